@@ -14,12 +14,31 @@ scaling: connections shard by GPU, the payload never crosses GPUs).
 
 Prints ONE JSON line (rank 0).  `roofline` is the unmask kernel's algorithmic
 bytes (h + 2L per frame) over its mean HIP-event duration in the
-timed region; `cpu_baseline` is the C restatement of the reference per-frame
-UnPacket pipeline (oracle/ws_ref.c) timed on this host's cores on a bounded
-sample of the same workload.
+timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5]
+A plain run does only what the headline figure needs: set-up (the batch
+synthesised on the device, one untimed decode that primes the context), W
+warmup steps, K timed steps, the outputs if --dump-outputs is given, the line.
+`--full` adds everything else, as measurements and checks of their own around
+the same timed region: the bit-exact verification of the batch on the device
+(before the timed region, and of the timed steps' own output after it), the
+streaming-copy ceiling (`roofline.copy_ceiling*`, --copy-reps) and the CPU
+baselines (`cpu_baseline*`: the C restatement of the reference per-frame
+UnPacket pipeline, oracle/ws_ref.c, timed on this host's cores on a bounded
+sample of the same workload; --no-cpu, --cpu-seconds).  Without --full those
+fields are null.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+`--dump-outputs DIR` writes what the last timed step's decode returned to its
+caller as DIR/<name>.npy (float64 / float32; ranks above 0 write
+<name>_rank<R>.npy): `summary`, `conn_out` and `frames` (the records' fields
+as columns, a seeded sample of the rows when there are more than
+DUMP_MAX_ROWS), `payload_sample` (the first DUMP_PAYLOAD_BYTES unmasked bytes
+of DUMP_PAYLOAD_FRAMES seeded frames, zero beyond a shorter frame's length)
+with `payload_sample_frames`, the records' indices.  Inputs and samples are
+seeded, so two builds run with the same arguments write comparable files.
 
 `python bench.py --gpus N` (N > 1) without a launcher starts its N ranks itself
 (torch.distributed.run as a child process, before anything touches a GPU) and
@@ -54,6 +73,67 @@ METRIC = "GiB/s WS payload unmasked (device-resident) + frames/s, 64 KiB masked 
 
 def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+DUMP_SEED = 0x64756d70
+DUMP_MAX_ROWS = 131072       # rows of `frames` / `conn_out` written (x 8 / 5 float64 columns)
+DUMP_PAYLOAD_FRAMES = 4096   # frames sampled for `payload_sample` ...
+DUMP_PAYLOAD_BYTES = 2048    # ... and the bytes taken from each (float32: 32 MiB)
+
+
+def _sample_rows(rng, n: int, k: int):
+    """Sorted indices of a seeded sample of k of n rows (every row when n <= k)."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(rng.choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname: str, out, rank: int) -> None:
+    """--dump-outputs: the arrays a caller of the decode receives (gev_amd.Batch:
+    summary, per-connection results, frame records, payload arena), as float
+    .npy files of at most ~46 MB in all.  Samples are by record index and by
+    payload_off + [0, length), never the arena's alignment padding, so every
+    value written is one the decode defines."""
+    import numpy as np
+    import torch
+    import gev_amd
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+
+    def save(name, a):
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+
+    rng = np.random.default_rng(DUMP_SEED)
+    s = out.summary_host()
+    save("summary", np.array([s[k] for k in ("frames", "payload_bytes", "payload_len", "errors", "status", "flags",
+                                             "run_frames")], dtype=np.float64))
+    dev = out.frames.device
+    co_idx = _sample_rows(rng, out.n_conns, DUMP_MAX_ROWS)
+    co = out.conn_out[torch.from_numpy(co_idx).to(dev)].cpu().numpy().reshape(-1).view(gev_amd.CONN_OUT_DTYPE)
+    save("conn_out", np.stack([co[k].astype(np.float64) for k in ("first_frame", "consumed", "payload_base",
+                                                                  "nframes", "status")], 1))
+    save("conn_out_rows", co_idx.astype(np.float64))
+    n = int(s["frames"])
+    fr_idx = _sample_rows(rng, n, DUMP_MAX_ROWS)
+    pl_idx = _sample_rows(rng, n, DUMP_PAYLOAD_FRAMES)
+
+    def records(idx):
+        return out.frames[torch.from_numpy(idx).to(dev)].cpu().numpy().reshape(-1).view(gev_amd.FRAME_DTYPE)
+
+    fr = records(fr_idx)
+    save("frames", np.stack([fr[k].astype(np.float64) for k in ("fin", "rsv", "opcode", "masked")]
+                            + [fr["mask"].copy().view("<u4")[:, 0].astype(np.float64)]
+                            + [fr[k].astype(np.float64) for k in ("length", "payload_off", "src_off")], 1))
+    save("frames_rows", fr_idx.astype(np.float64))
+    pr = records(pl_idx)
+    take = np.minimum(pr["length"], DUMP_PAYLOAD_BYTES).astype(np.int64)
+    col = np.arange(DUMP_PAYLOAD_BYTES, dtype=np.int64)[None, :]
+    valid = col < take[:, None]
+    at = np.where(valid, pr["payload_off"].astype(np.int64)[:, None] + col, 0)
+    got = out.payload[torch.from_numpy(at.reshape(-1)).to(dev)].cpu().numpy().reshape(at.shape)
+    save("payload_sample", np.where(valid, got, 0).astype(np.float32))
+    save("payload_sample_frames", pl_idx.astype(np.float64))
 
 
 def build_layout(name: str, rank: int, conns: int | None, world: int = 1, scaling: str = "weak"):
@@ -328,11 +408,17 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None,
                     help="weak: each GPU its own batch of the config's shape (default for c2/c3/c5); "
                          "strong: one global batch sharded over the GPUs by LPT (default for c4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the batch bit-exact on the device, measure the streaming-copy ceiling "
+                         "(--copy-reps) and time the CPU baselines (--no-cpu, --cpu-seconds); off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-threads-multi", type=int, default=0,
                     help="threads of the all-cores CPU baseline (0 = every CPU this process may use)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--copy-reps", type=int, default=5, help="streaming-copy ceiling reps (0 = skip)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--copy-reps", type=int, default=5,
+                    help="with --full: streaming-copy ceiling reps (0 = skip)")
     ap.add_argument("--copy-interleave", type=int, default=0,
                     help="R rounds of [decode, size-matched aligned copy] after the timed region: the unmask "
                          "against the copy rate in the same clock state (0 = skip)")
@@ -422,16 +508,20 @@ def main():
     max_frames, cap = lay.n_frames, lay.payload_padded
     out = eng.alloc_batch(lay.n_conns, max_frames, cap)
 
-    # correctness gate (outside the timed region): decode(mask(P)) == P on every byte
+    # one untimed decode primes the context (the split walk's auto choice looks
+    # at it); --full: the correctness gate on it, decode(mask(P)) == P on every byte
     eng.decode_async(arena, lay.arena_bytes, conns, lay.n_conns, out, max_frames, cap)
-    mism = torch.zeros(1, dtype=torch.int64, device=dev)
-    eng.verify(desc, lay.n_frames, lay.seed, out, mism)
+    if args.full:
+        mism = torch.zeros(1, dtype=torch.int64, device=dev)
+        eng.verify(desc, lay.n_frames, lay.seed, out, mism)
+        torch.cuda.synchronize()
+        s = out.summary_host()
+        mismatch = int(mism.item())
+        if mismatch or int(s["frames"]) != lay.n_frames or int(s["payload_len"]) != lay.payload_len:
+            raise SystemExit(f"verification failed: mismatch={mismatch} frames={int(s['frames'])}")
     torch.cuda.synchronize()
-    s = out.summary_host()
-    mismatch = int(mism.item())
-    if mismatch or int(s["frames"]) != lay.n_frames or int(s["payload_len"]) != lay.payload_len:
-        raise SystemExit(f"verification failed: mismatch={mismatch} frames={int(s['frames'])}")
-    log(f"rank {rank}: setup+verify {time.time() - t_setup:.1f}s, bit-exact")
+    log(f"rank {rank}: setup{'+verify' if args.full else ''} {time.time() - t_setup:.1f}s"
+        f"{', bit-exact' if args.full else ''}")
 
     counts = torch.zeros(3, dtype=torch.int64, device=dev)
     sel = torch.tensor([0, 2, 3], dtype=torch.int64, device=dev)
@@ -477,9 +567,9 @@ def main():
         phases = [a + b for a, b in zip(phases, ph)]
         calls += cl
     elapsed = dist.max_over_ranks(t1 - t0, dev)
-    # the timed steps' own output checked too (outside the timed region): every
-    # slot's last batch, decode(mask(P)) == P on every byte
-    for k in range(M):
+    # --full: the timed steps' own output checked too (outside the timed
+    # region): every slot's last batch, decode(mask(P)) == P on every byte
+    for k in range(M if args.full else 0):
         mism.zero_()
         engs[k].verify(desc, lay.n_frames, lay.seed, outs[k], mism)
         torch.cuda.synchronize()
@@ -489,7 +579,10 @@ def main():
                              f"status={int(sk['status'])}")
     del desc
 
-    last = engs[(args.steps + args.warmup - 1) % M]  # the context of the last step
+    last_slot = (args.steps + args.warmup - 1) % M  # the slot of the last step
+    last = engs[last_slot]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs[last_slot], rank)
     walk_info = {"split_lanes": last.last_split_lanes, "split_fallbacks": last.last_split_fallbacks}
     # achievable-bandwidth ceiling on this box, after the timed region: the
     # unmask kernel's streaming loop minus XOR / frame lookup (gevws_copy_async)
@@ -500,7 +593,7 @@ def main():
     # of the four is the ceiling
     copy_gbps = None
     copy_by_load = {}
-    if args.copy_reps > 0:
+    if args.full and args.copy_reps > 0:
         from gev_amd.workloads import header_len
         src_off = int(header_len(lay.desc["length"][:1], lay.desc["masked"][:1], lay.desc["len_form"][:1])[0])
         n_copy = min(lay.payload_padded, lay.arena_bytes - src_off) // 16 * 16
@@ -608,11 +701,11 @@ def main():
                      "copy_ceiling_by_load": copy_by_load or None,
                      "frac_of_copy_ceiling": None if copy_gbps is None else round(achieved / copy_gbps, 4),
                      **({"copy_interleaved": interleaved} if interleaved else {})},
-        "verified_bit_exact": True,
+        "verified_bit_exact": True if args.full else None,
         "frame_size_histogram": (size_histogram(glob) if args.config in ("c4", "c5") else None),
         "cpu_baseline": None,
     }
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         log("cpu baseline (1 thread)...")
         result["cpu_baseline"] = cpu_baseline(args.config, args.cpu_seconds, 1)
         nt = args.cpu_threads_multi or all_host_threads()

@@ -7,4 +7,4 @@ run() { local name=$1 to=$2; shift 2; echo "== $name"
 
 run srv_c3 600 python tools/bench_server.py --config c3 --reps 5 || exit $?
 export GEV_DIST_BACKEND=gloo
-run bench_2rank 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --config c2 --steps 20 --warmup 3 || exit $?
+run bench_2rank 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --config c2 --steps 20 --warmup 3 || exit $?

@@ -14,7 +14,7 @@ rc=$?; echo "trace rc=$rc"; tail -2 $OUT/${PREFIX:-prof}_trace.log; [ $rc -eq 0 
 for C in FETCH_SIZE WRITE_SIZE; do
   echo "== pmc $C"
   timeout -k 10 400 rocprofv3 --pmc $C -d $OUT/${PREFIX:-prof}_pmc_$C -o bench --output-format csv \
-    -- python3 $R/bench.py --steps 2 --warmup 0 --no-cpu ${BENCH_ARGS} > $OUT/${PREFIX:-prof}_pmc_$C.log 2>&1
+    -- python3 $R/bench.py --full --steps 2 --warmup 0 --no-cpu ${BENCH_ARGS} > $OUT/${PREFIX:-prof}_pmc_$C.log 2>&1
   rc=$?; echo "pmc $C rc=$rc"; tail -2 $OUT/${PREFIX:-prof}_pmc_$C.log; [ $rc -eq 0 ] || exit $rc
 done
 find $OUT/${PREFIX:-prof}_* -name "*.csv" | head -20

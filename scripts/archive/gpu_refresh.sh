@@ -14,6 +14,6 @@ step() {  # step <name> <timeout> <cmd...>
 step pytest_gpu 900 python -m pytest tests -m gpu -q -p no:cacheprovider -x
 rc=$?; tail -5 $OUT/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 step smoke 180 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-step bench 400 python bench.py || exit $?
+step bench 400 python bench.py --full || exit $?
 cat $OUT/bench.log
 bash $R/scripts/gpu_profile.sh

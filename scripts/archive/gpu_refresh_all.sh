@@ -8,10 +8,10 @@ run() { local name=$1 to=$2; shift 2; echo "== $name"
   echo "$name rc=$rc"; tail -2 $OUT/$name.err; return $rc; }
 run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread; rc=$?; tail -3 $OUT/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 run smoke 180 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-run bench 500 python bench.py || exit $?
+run bench 500 python bench.py --full || exit $?
 cat $OUT/bench.log
 for c in c2 c4 c5; do
-  run bench_$c 500 python bench.py --config $c --steps 10 --warmup 2 --no-cpu || exit $?
+  run bench_$c 500 python bench.py --full --config $c --steps 10 --warmup 2 --no-cpu || exit $?
   tail -c 600 $OUT/bench_$c.log; echo
 done
 PREFIX=prof_c3 bash scripts/gpu_profile.sh || exit $?

@@ -6,7 +6,7 @@ run() { local name=$1 to=$2; shift 2; echo "== $name"
   echo "$name rc=$rc"; tail -3 $OUT/$name.err; return $rc; }
 run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread; rc=$?; tail -4 $OUT/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 run smoke 180 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-run bench 400 python bench.py --cpu-seconds 4 || exit $?
+run bench 400 python bench.py --full --cpu-seconds 4 || exit $?
 cat $OUT/bench.log
-run bench_c4 400 python bench.py --config c4 --steps 10 --warmup 2 --no-cpu || exit $?
+run bench_c4 400 python bench.py --full --config c4 --steps 10 --warmup 2 --no-cpu || exit $?
 cat $OUT/bench_c4.log

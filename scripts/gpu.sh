@@ -13,7 +13,7 @@
 # test  <pytest args>      python -m pytest -x -v (thread timeout per test)
 # bench <tag> <bench args> bench.py --no-cpu --copy-reps 0 (unless given) --steps 10 --warmup 2 (unless
 #                          given); the JSON line, tagged, appended to $OUT/${JSONL:-bench}.jsonl
-# full  <tag> <bench args> bench.py exactly as given (the contract line: CPU legs, copy ceiling)
+# full  <tag> <bench args> bench.py --full with the arguments given (verification, CPU legs, copy ceiling)
 # prof  <tag> <bench args> the bench under rocprofv3 --kernel-trace --stats -> $OUT/prof_<tag>/
 # pmc   <tag> <ctrs> -- <bench args>  one rocprofv3 --pmc pass (counters comma-separated)
 # py    <args>             python <args>
@@ -39,6 +39,7 @@ for step in "$@"; do
     bench|full)
       tag=$1; shift
       extra=""
+      [ $kind = full ] && extra=" --full"
       if [ $kind = bench ]; then
         [[ " $* " == *" --steps "* ]] || extra="$extra --steps 10"
         [[ " $* " == *" --warmup "* ]] || extra="$extra --warmup 2"

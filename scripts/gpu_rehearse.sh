@@ -10,5 +10,5 @@ run() { local name=$1 to=$2; shift 2; echo "== $name"
   timeout -k 10 $to "$@" > $OUT/$name.log 2> $OUT/$name.err; local rc=$?
   echo "$name rc=$rc"; tail -3 $OUT/$name.err; tail -c 900 $OUT/$name.log; echo; return $rc; }
 export GEV_DIST_BACKEND=gloo
-run rehearse_c2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --config c2 --steps 10 --warmup 2 || exit $?
-run rehearse_c4 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --config c4 --steps 5 --warmup 1 || exit $?
+run rehearse_c2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --config c2 --steps 10 --warmup 2 || exit $?
+run rehearse_c4 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --full --gpus 2 --config c4 --steps 5 --warmup 1 || exit $?
