@@ -97,6 +97,9 @@ __global__ __launch_bounds__(256) void k_synth_verify(const gevws_synth_desc* __
       bad += fr.src_off != d.hdr_off + synth_hlen(d);
       bad += (fr.payload_off & 15) != 0;
     }
+    // misaligned record: counted above, its payload never loaded (the u32x4
+    // load below needs the 16-byte boundary); block-uniform like the range guard
+    if (fr.payload_off & 15) continue;
     const uint64_t padded = round16(d.length);
     for (uint64_t i = (uint64_t)threadIdx.x * 16; i < padded; i += 256 * 16) {
       u32x4 want = plain16(seed, g, i);

@@ -77,8 +77,11 @@ class Layout:
         return self.header_bytes + 2 * self.payload_len
 
 
-def _assemble(name: str, lengths_per_conn, b0_per_conn, masked_per_conn, seed: int,
+def assemble(name: str, lengths_per_conn, b0_per_conn, masked_per_conn, seed: int,
               len_form_per_conn=None) -> Layout:
+    """A layout from per-connection arrays of payload lengths, first header
+    bytes (FIN | RSV | opcode) and masked flags; len_form_per_conn (7 / 16 /
+    64 per frame) picks the length encoding, the minimal one by default."""
     lengths = np.concatenate(lengths_per_conn).astype(np.uint64) if lengths_per_conn else np.zeros(0, np.uint64)
     b0 = np.concatenate(b0_per_conn).astype(np.uint8) if b0_per_conn else np.zeros(0, np.uint8)
     masked = np.concatenate(masked_per_conn).astype(np.uint8) if masked_per_conn else np.zeros(0, np.uint8)
@@ -162,7 +165,7 @@ def config_c4(total_payload: int, n_conns: int = 8192, alpha: float = 1.1, lo: i
         lengths.append(L)
         b0s.append(np.full(L.shape[0], 0x82, np.uint8))
         ms.append(np.ones(L.shape[0], np.uint8))
-    return _assemble(f"C4: power-law {lo}B-{hi}B alpha={alpha}", lengths, b0s, ms, seed)
+    return assemble(f"C4: power-law {lo}B-{hi}B alpha={alpha}", lengths, b0s, ms, seed)
 
 
 def config_c5(n_conns: int = 64, messages_per_conn: int = 4, message_bytes: int = 1 << 20,
@@ -190,7 +193,7 @@ def config_c5(n_conns: int = 64, messages_per_conn: int = 4, message_bytes: int 
         lengths.append(np.array(L, np.int64))
         b0s.append(np.array(B, np.uint8))
         ms.append(np.ones(len(L), np.uint8))
-    return _assemble("C5: fragmented text + ping/pong", lengths, b0s, ms, seed)
+    return assemble("C5: fragmented text + ping/pong", lengths, b0s, ms, seed)
 
 
 def shard_bounds(conn_lens: np.ndarray, world: int) -> list:

@@ -479,8 +479,10 @@ int gevws_synth_async(gevws_ctx *ctx, void *stream, uint8_t *d_in, const gevws_s
 /* Property check of a decoded batch against the generator: counts mismatching
  * header fields, payload bytes (decode(mask(P)) == P) and non-zero pad bytes
  * into *d_mismatch (device uint64, accumulated).  Frame g of the batch must be
- * frame g of d_desc; records pointing outside [0, payload_cap) count as
- * mismatches and are not dereferenced. */
+ * frame g of d_desc; records pointing outside [0, payload_cap) or not 16-byte
+ * aligned count as mismatches and are not dereferenced: one outside the arena
+ * counts its length + 1 and nothing else, a misaligned one counts its header
+ * fields (the alignment among them) and none of its bytes. */
 int gevws_synth_verify_async(gevws_ctx *ctx, void *stream, const gevws_synth_desc *d_desc,
                              uint64_t n_frames, uint64_t seed, const gevws_frame *d_frames,
                              const uint8_t *d_payload, uint64_t payload_cap, uint64_t *d_mismatch);

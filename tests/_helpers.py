@@ -99,6 +99,96 @@ def post_and_wait(engine, flag, a: np.ndarray, conns: np.ndarray, timeout: float
     return host_result(out), (d_in, d_conns, out)
 
 
+def verify_host(desc: np.ndarray, seed: int, frames: np.ndarray, payload: np.ndarray, payload_cap: int) -> int:
+    """The contract of gevws_synth_verify_async (include/gevws.h), restated
+    frame by frame in numpy: the count the device verifier must add to its
+    counter for the records `frames` (FRAME_DTYPE, frame g at index g) and the
+    arena `payload` of a decode of the layout `desc` (SYNTH_DTYPE).
+
+    A record outside [0, payload_cap) counts length + 1 and nothing else.
+    Otherwise every header field that differs from the descriptor counts one
+    (fin, rsv, opcode, masked, the 4-byte key as one field -- 0 when unmasked
+    --, length, src_off == hdr_off + header length, payload_off 16-aligned),
+    and, unless the record is misaligned, so does every byte of the
+    round16(length) bytes at payload_off that differs from the generator's
+    plaintext followed by zeros."""
+    from gev_amd import workloads
+    n = int(desc.shape[0])
+    hlen = workloads.header_len(desc["length"].astype(np.int64), desc["masked"], desc["len_form"].astype(np.int64))
+    # columns as python ints (exact at 2**63 and beyond), then frame by frame
+    d_len, d_b0, d_masked, d_key = (desc[k].tolist() for k in ("length", "b0", "masked", "mask"))
+    src = (desc["hdr_off"].astype(np.int64) + hlen).tolist()
+    f_fin, f_rsv, f_op, f_masked, f_len, f_off, f_src = (
+        frames[k][:n].tolist() for k in ("fin", "rsv", "opcode", "masked", "length", "payload_off", "src_off"))
+    f_key = np.ascontiguousarray(frames["mask"][:n]).view("<u4").reshape(-1).tolist()
+    bad = 0
+    for g in range(n):
+        L, off = d_len[g], f_off[g]
+        padded = (L + 15) // 16 * 16
+        if off > payload_cap or padded > payload_cap - off:
+            bad += L + 1
+            continue
+        b0 = d_b0[g]
+        bad += f_fin[g] != b0 >> 7
+        bad += f_rsv[g] != (b0 >> 4) & 7
+        bad += f_op[g] != b0 & 15
+        bad += f_masked[g] != d_masked[g]
+        bad += f_key[g] != (d_key[g] if d_masked[g] else 0)
+        bad += f_len[g] != L
+        bad += f_src[g] != src[g]
+        bad += off % 16 != 0
+        if off % 16 or L == 0:
+            continue
+        want = np.zeros(padded, np.uint8)
+        want[:L] = np.frombuffer(workloads.plaintext(seed, g, L), np.uint8)
+        bad += int(np.count_nonzero(payload[off:off + padded] != want))
+    return bad
+
+
+def expected_conn_table(layout):
+    """What a decode of a synthetic layout must report per connection, from
+    layout.desc and layout.conns alone: (nframes, first_frame, payload_base),
+    int64 each.  Records are ordered by connection, then stream order, and
+    the arena is packed: every payload starts where the one before it ended,
+    rounded up to 16 bytes (include/gevws.h; oracle/ws_ref.c lays it out so)."""
+    hdr = layout.desc["hdr_off"].astype(np.int64)
+    assert np.all(np.diff(hdr) > 0)
+    lo = np.searchsorted(hdr, layout.conns[:, 0], side="left")
+    hi = np.searchsorted(hdr, layout.conns[:, 0] + layout.conns[:, 1], side="left")
+    nframes = (hi - lo).astype(np.int64)
+    first = np.cumsum(nframes) - nframes
+    assert np.array_equal(first, lo) and int(nframes.sum()) == layout.n_frames  # the layout itself
+    padded = (layout.desc["length"].astype(np.int64) + 15) // 16 * 16
+    pref = np.concatenate([[0], np.cumsum(padded)]).astype(np.int64)
+    return nframes, first, pref[first]
+
+
+def check_batch_structure(out, layout, desc_dev) -> None:
+    """Every connection's nframes / first_frame / status / payload_base and
+    every record's payload_off of a decode of a synthetic layout -- what the
+    device verifier cannot see: it accepts any in-range aligned payload_off
+    whose bytes match.  The per-frame part runs on the device over the whole
+    record tensor (about 40 bytes of temporaries per frame)."""
+    import torch
+    nframes, first, base = expected_conn_table(layout)
+    co = out.conn_out_host()
+    assert np.array_equal(co["nframes"].astype(np.int64), nframes)
+    assert np.array_equal(co["first_frame"].astype(np.int64), first)
+    assert not co["status"].any()
+    assert np.array_equal(co["payload_base"].astype(np.int64), base)
+    n = layout.n_frames
+    if n == 0:
+        return
+    rec = out.frames[:n].view(torch.int64)              # [n, 4]: header word, length, payload_off, src_off
+    length = desc_dev.view(torch.int64).view(-1, 3)[:n, 1]
+    want = (length + 15) & ~15
+    end = torch.cumsum(want, 0)
+    assert int(end[-1].item()) == layout.payload_padded
+    want = end.sub_(want)                               # exclusive prefix sum of the rounded lengths
+    wrong = int((rec[:, 2] != want).sum().item())
+    assert wrong == 0, f"{layout.name}: {wrong} records off the packed arena layout"
+
+
 def oracle_run_frames(want, conns) -> int:
     """summary.run_frames from the oracle's records: frames whose size (h + L)
     equals the size of the frame before them on the same connection."""

@@ -11,7 +11,8 @@ import pytest
 import gev_amd
 from oracle import ref
 from oracle import ws_oracle as wo
-from tests._helpers import assert_matches_oracle, gpu_decode, host_result, pack_streams, random_stream
+from tests._helpers import (assert_matches_oracle, check_batch_structure, gpu_decode, host_result, pack_streams,
+                            random_stream)
 
 pytestmark = pytest.mark.gpu
 
@@ -275,6 +276,8 @@ def _synth_decode_verify(engine, layout, check_slice_conns: int = 2):
     assert int(mism.item()) == 0
     co = out.conn_out_host()
     assert np.array_equal(co["consumed"].astype(np.int64), layout.conns[:, 1])
+    # what the verifier cannot see, for every connection and every record
+    check_batch_structure(out, layout, desc)
     # oracle cross-check of the first connections' streams, byte for byte
     k = min(check_slice_conns, layout.n_conns)
     end = int(layout.conns[k - 1, 0] + layout.conns[k - 1, 1])
@@ -377,6 +380,7 @@ def _c4_full(engine, lay, n_check: int = 64, expect_split=None):
     dev = torch.device("cuda", engine.device)
     free, _ = torch.cuda.mem_get_info(engine.device)
     need = lay.arena_bytes + lay.payload_padded + lay.n_frames * 32 + lay.arena_bytes // 4 + (2 << 30)
+    need += lay.n_frames * (24 + 40)  # the descriptors, check_batch_structure's temporaries
     if free < need:
         pytest.fail(f"{lay.name}: needs {need / 2**30:.1f} GiB of HBM, {free / 2**30:.1f} GiB free")
     arena = torch.empty(lay.arena_bytes + gev_amd.IN_PAD, dtype=torch.uint8, device=dev)
@@ -397,6 +401,7 @@ def _c4_full(engine, lay, n_check: int = 64, expect_split=None):
     engine.verify(desc, lay.n_frames, lay.seed, out, mism)
     torch.cuda.synchronize()
     assert int(mism.item()) == 0
+    check_batch_structure(out, lay, desc)
     counts = np.diff(np.searchsorted(lay.desc["hdr_off"].astype(np.int64),
                                      np.concatenate([lay.conns[:, 0], [lay.arena_bytes]])))
     longest = int(np.argmax(counts))
@@ -650,6 +655,7 @@ def test_every_unmask_variant_device_synth(engine, cfg):
             s = out.summary_host()
             assert int(s["frames"]) == lay.n_frames and int(s["payload_len"]) == lay.payload_len, i
             assert int(mism.item()) == 0, (i, engine.variant_name(i))
+            check_batch_structure(out, lay, desc)
             i += 1
     finally:
         engine.set_tuning(_abi.TUNE_UNMASK_VARIANT, 0)
