@@ -23,6 +23,8 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi
+from ._abi import (MSG_BEGIN, MSG_END, MSG_ERR_CONTINUATION, MSG_ERR_CONTROL, MSG_ERR_INTERLEAVE, MSG_ERR_OPCODE,
+                   MSG_ERR_RSV, MSG_ERR_UTF8, MSG_OK)
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
                    SUMMARY_UNORDERED, TILE, Header)
@@ -42,7 +44,14 @@ OUT_FRAME_DTYPE = np.dtype([("fin", "u1"), ("rsv", "u1"), ("opcode", "u1"), ("ma
                             ("payload_off", "<u8"), ("payload_len", "<u8")])
 SYNTH_DTYPE = np.dtype([("hdr_off", "<u8"), ("length", "<u8"), ("mask", "<u4"), ("b0", "u1"),
                         ("len_form", "u1"), ("masked", "u1"), ("pad", "u1")])
+MSG_STATE_DTYPE = np.dtype([("opcode", "u1"), ("failed", "u1"), ("utf8_n", "u1"), ("utf8", "u1", (3,)),
+                            ("reserved", "u1", (2,))])
+MESSAGE_DTYPE = np.dtype([("first_frame", "<u8"), ("length", "<u8"), ("conn", "<u4"), ("nframes", "<u4"),
+                          ("opcode", "u1"), ("flags", "u1"), ("status", "u1"), ("reserved", "u1", (5,))])
+CONN_MSG_DTYPE = np.dtype([("first_message", "<u8"), ("error_frame", "<u8"), ("nmessages", "<u4"),
+                           ("error", "<i4"), ("reserved", "<u8")])
 assert FRAME_DTYPE.itemsize == 32 and CONN_OUT_DTYPE.itemsize == 32
+assert MSG_STATE_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 32 and CONN_MSG_DTYPE.itemsize == 32
 assert SUMMARY_DTYPE.itemsize == 64 and SYNTH_DTYPE.itemsize == 24
 
 
@@ -52,6 +61,12 @@ def status_string(st: int) -> str:
 
 def device_count() -> int:
     return lib.gevws_device_count()
+
+
+def utf8_valid(b: bytes) -> bool:
+    """gevws_utf8_valid: unicode/utf8.Valid on host bytes (the rule the device pass applies)."""
+    b = bytes(b)
+    return bool(lib.gevws_utf8_valid(ctypes.c_char_p(b), len(b)))
 
 
 def _torch():
@@ -88,6 +103,36 @@ class Batch:
     def payload_host(self) -> np.ndarray:
         n = int(self.summary_host()["payload_bytes"])
         return self.payload[:n].cpu().numpy()
+
+
+@dataclass
+class Messages:
+    """Device-resident result of one message pass (Engine.messages)."""
+    messages: "object"    # uint8 [max_messages, 32] (gevws_message records)
+    msg_of: "object"      # int64 [max_frames]       (frame -> message, -1: none)
+    conn_msg: "object"    # uint8 [n_conns, 32]      (gevws_conn_msg)
+    state: "object"       # uint8 [n_conns, 8]       (gevws_msg_state after the pass) or None
+    summary: "object"     # uint8 [64]               (gevws_summary)
+    n_conns: int
+    n_frames: int
+
+    def summary_host(self) -> np.ndarray:
+        return self.summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
+
+    def messages_host(self) -> np.ndarray:
+        n = int(self.summary_host()["frames"])
+        return self.messages[:n].cpu().numpy().reshape(-1).view(MESSAGE_DTYPE)
+
+    def msg_of_host(self) -> np.ndarray:
+        return self.msg_of[: self.n_frames].cpu().numpy()
+
+    def conn_msg_host(self) -> np.ndarray:
+        return self.conn_msg[: self.n_conns].cpu().numpy().reshape(-1).view(CONN_MSG_DTYPE)
+
+    def state_host(self) -> Optional[np.ndarray]:
+        if self.state is None:
+            return None
+        return self.state[: self.n_conns].cpu().numpy().reshape(-1).view(MSG_STATE_DTYPE)
 
 
 class _DevAddr:
@@ -387,6 +432,47 @@ class Engine:
         rep_host = replies[:nr].cpu().numpy().reshape(-1).view(OUT_FRAME_DTYPE)
         wire, _ = self.encode(rep_host, out.payload, int(rep_host["payload_len"].sum()) + 14 * nr)
         return wire, reply_of[:n].cpu().numpy(), ds
+
+    # -------------------------------------------------------------- message layer
+    def messages_async(self, frames, max_frames: int, conn_out, n_conns: int, decoded, payload, state, messages,
+                       max_messages: int, msg_of, conn_msg, summary, stream=None) -> None:
+        """gevws_messages_async on device tensors: fragment assembly, the RFC
+        6455 frame checks and the UTF-8 check of text messages behind a decode
+        (state: uint8 [n_conns, 8] read and rewritten, or None = all fresh)."""
+        st = lib.gevws_messages_async(
+            self._ctx, _stream_handle(stream), frames.data_ptr(), max_frames, conn_out.data_ptr(), n_conns,
+            decoded.data_ptr(), payload.data_ptr(), state.data_ptr() if state is not None else None,
+            messages.data_ptr(), max_messages, msg_of.data_ptr(), conn_msg.data_ptr(), summary.data_ptr())
+        if st != OK:
+            raise RuntimeError(f"gevws_messages_async: {status_string(st)}")
+
+    def messages(self, out: "Batch", state=None, max_messages: Optional[int] = None, stream=None) -> "Messages":
+        """The message pass over a decoded batch; `state` (uint8 [n_conns, 8]
+        device tensor) carries open messages from pass to pass and is updated
+        in place.  Grows the message table once on ERR_CAPACITY (the state is
+        untouched by the pass that did not fit)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        n = int(out.summary_host()["frames"]) if int(out.summary_host()["status"]) == OK else 0
+        if max_messages is None:
+            max_messages = n
+        for attempt in range(2):
+            res = Messages(messages=torch.empty((max(max_messages, 1), 32), dtype=torch.uint8, device=dev),
+                           msg_of=torch.empty(max(n, 1), dtype=torch.int64, device=dev),
+                           conn_msg=torch.zeros((max(out.n_conns, 1), 32), dtype=torch.uint8, device=dev),
+                           state=state, summary=torch.zeros(64, dtype=torch.uint8, device=dev),
+                           n_conns=out.n_conns, n_frames=n)
+            self.messages_async(out.frames, n, out.conn_out, out.n_conns, out.summary, out.payload, state,
+                                res.messages, max_messages, res.msg_of, res.conn_msg, res.summary, stream)
+            torch.cuda.synchronize(self.device)
+            s = res.summary_host()
+            if int(s["status"]) == ERR_CAPACITY and attempt == 0:
+                max_messages = int(s["frames"])
+                continue
+            if int(s["status"]) != OK:
+                raise RuntimeError(f"messages: {status_string(int(s['status']))}")
+            return res
+        raise RuntimeError("messages: capacity retry failed")
 
     def set_completion_flag(self, arena: Optional["PinnedArena"], offset: int = 0) -> None:
         """gevws_ctx_set_completion_flag: the one-launch kernels store their

@@ -53,6 +53,17 @@ TUNE_RETIRED = (5, 6, 9, 10, 11, 12)  # round 1-3 measurement knobs, rejected
 TUNE_SPLIT_MIN_BYTES = 13  # split walk: bytes per segment at least (default 16 384)
 TUNE_SPLIT_LANES_PER_CU = 14  # split walk auto: lanes per CU at most (default 512)
 
+# message layer (gevws_messages_async): verdicts and message flags
+MSG_OK = 0
+MSG_ERR_RSV = 1
+MSG_ERR_OPCODE = 2
+MSG_ERR_CONTROL = 3
+MSG_ERR_CONTINUATION = 4
+MSG_ERR_INTERLEAVE = 5
+MSG_ERR_UTF8 = 6
+MSG_BEGIN = 1
+MSG_END = 2
+
 IN_PAD = 64
 MEM_DEFAULT, MEM_FINE, MEM_UNCACHED = 0, 1, 2  # gevws_device_alloc kinds
 SUMMARY_UNORDERED = 1  # summary.flags: connection table not in increasing input order
@@ -120,6 +131,23 @@ class SynthDesc(ctypes.Structure):
                 ("pad", ctypes.c_uint8)]
 
 
+class MsgState(ctypes.Structure):
+    """gevws_msg_state: a connection's carry between message passes (zero = fresh)."""
+    _fields_ = [("opcode", ctypes.c_uint8), ("failed", ctypes.c_uint8), ("utf8_n", ctypes.c_uint8),
+                ("utf8", ctypes.c_uint8 * 3), ("reserved", ctypes.c_uint8 * 2)]
+
+
+class Message(ctypes.Structure):
+    _fields_ = [("first_frame", ctypes.c_uint64), ("length", ctypes.c_uint64), ("conn", ctypes.c_uint32),
+                ("nframes", ctypes.c_uint32), ("opcode", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("status", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 5)]
+
+
+class ConnMsg(ctypes.Structure):
+    _fields_ = [("first_message", ctypes.c_uint64), ("error_frame", ctypes.c_uint64),
+                ("nmessages", ctypes.c_uint32), ("error", ctypes.c_int32), ("reserved", ctypes.c_uint64)]
+
+
 class Reject(ctypes.Structure):
     """gevws_reject: RejectConnectionError options (ws/errors.go:81-129)."""
     _fields_ = [("code", ctypes.c_int32), ("plain", ctypes.c_int32), ("reason", ctypes.c_void_p),
@@ -164,6 +192,7 @@ assert ctypes.sizeof(Reject) == 40 and ctypes.sizeof(UpgraderHooks) == 72 and ct
 assert ctypes.sizeof(Header) == 16 and ctypes.sizeof(Frame) == 32
 assert ctypes.sizeof(ConnIn) == 16 and ctypes.sizeof(ConnOut) == 32
 assert ctypes.sizeof(Summary) == 64 and ctypes.sizeof(SynthDesc) == 24
+assert ctypes.sizeof(MsgState) == 8 and ctypes.sizeof(Message) == 32 and ctypes.sizeof(ConnMsg) == 32
 
 P = ctypes.c_void_p
 U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -208,6 +237,9 @@ SIGNATURES = {
                                                   ctypes.c_uint64, P, P, P, P, ctypes.c_uint64, P, P]),
     "gevws_dispatch_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_int, P, ctypes.c_uint64,
                                             ctypes.c_uint64, P, P, P]),
+    "gevws_messages_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint32, P, P, P, P,
+                                            ctypes.c_uint64, P, P, P]),
+    "gevws_utf8_valid": (ctypes.c_int, [P, ctypes.c_uint64]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),
     "gevws_synth_async": (ctypes.c_int, [P, P, P, P, ctypes.c_uint64, ctypes.c_uint64]),
     "gevws_synth_verify_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P,

@@ -65,14 +65,6 @@ constexpr int kEncSlabs = 16;
 constexpr int kEncLaneTiles = 4;
 // k_encode6's run mode 2: one run counter per XCD, 64 bytes apart (zeroed by k_enc_emit)
 constexpr uint32_t kEnc6Counters = 8;
-// The frame count of a chained pass (decode -> dispatch -> encode with no host
-// round trip): the producing step's summary gates the consumer -- its frames,
-// or none when it failed (a capacity error leaves stale records behind).
-__device__ __forceinline__ uint64_t gated_count(uint64_t n, const gevws_summary* __restrict__ gate) {
-  if (!gate) return n;
-  const gevws_summary g = *gate;
-  return g.status != GEVWS_OK ? 0 : (g.frames < n ? g.frames : n);
-}
 
 // Also writes each frame's wire size (h + L) into out_off[f], which k_enc_emit
 // turns into the offset in place: the emit pass reads 8 bytes per frame

@@ -284,6 +284,15 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t x) {
   return (uint64_t)uniform32((uint32_t)x) | ((uint64_t)uniform32((uint32_t)(x >> 32)) << 32);
 }
 
+// The frame count of a chained pass (decode -> dispatch -> encode with no host
+// round trip): the producing step's summary gates the consumer -- its frames,
+// or none when it failed (a capacity error leaves stale records behind).
+__device__ __forceinline__ uint64_t gated_count(uint64_t n, const gevws_summary* __restrict__ gate) {
+  if (!gate) return n;
+  const gevws_summary g = *gate;
+  return g.status != GEVWS_OK ? 0 : (g.frames < n ? g.frames : n);
+}
+
 // ------------------------------------------------------------------ 2. scan of block partials
 // SPLIT (decode): field 3 holds errors in its low 32 bits and the count of
 // out-of-order connections in its high 32 (k_walk_count) -> summary.errors and

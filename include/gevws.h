@@ -391,6 +391,122 @@ int gevws_handle_decoded_async(gevws_ctx *ctx, void *stream, const gevws_frame *
                                gevws_summary *d_disp_summary, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off,
                                gevws_summary *d_enc_summary);
 
+/* ---------------------------------------------------------------- message layer
+ * What the reference leaves to the user's OnMessage (wrap.go:71 hands every
+ * data frame's payload over as it is): RFC 6455 message assembly and checks
+ * for a server reading client frames with no extension negotiated -- section
+ * 5.2 (RSV bits, reserved opcodes), 5.4 (fragmentation), 5.5 (control frames
+ * are not fragmented and carry <= 125 bytes) and 8.1 (text is UTF-8).  An
+ * opt-in step behind a decode, beside gevws_dispatch_decoded_async.
+ *
+ * For each connection with status == GEVWS_OK its frames are taken in order,
+ * starting from its carry state; the first hit of these checks, in this
+ * order, fails the connection at that frame:
+ *   1. rsv != 0                                      GEVWS_MSG_ERR_RSV           (5.2)
+ *   2. opcode 3-7 or 0xB-0xF                         GEVWS_MSG_ERR_OPCODE        (5.2)
+ *   3. control frame, fin == 0 or length > 125       GEVWS_MSG_ERR_CONTROL       (5.5)
+ *   4. opcode 0 with no message open                 GEVWS_MSG_ERR_CONTINUATION  (5.4)
+ *   5. opcode 1 / 2 while a message is open          GEVWS_MSG_ERR_INTERLEAVE    (5.4)
+ *   6. in a text message, a byte that cannot continue a valid UTF-8 sequence
+ *      (at the frame holding it), or the message's FIN frame ending inside a
+ *      sequence (at the FIN frame)                   GEVWS_MSG_ERR_UTF8          (8.1)
+ * UTF-8 is strict, as unicode/utf8.Valid: no overlong forms, no surrogates,
+ * nothing above U+10FFFF.  The sequence state runs across the fragments of
+ * one text message (control frames in between do not disturb it); payloads of
+ * binary messages and of control frames are not validated (dispatch checks
+ * the close reason).  A caller closes a failed connection with status 1002
+ * (protocol error) for errors 1-5 and 1007 (invalid payload data) for 6
+ * (section 7.4.1). */
+enum {
+    GEVWS_MSG_OK = 0,
+    GEVWS_MSG_ERR_RSV = 1,
+    GEVWS_MSG_ERR_OPCODE = 2,
+    GEVWS_MSG_ERR_CONTROL = 3,
+    GEVWS_MSG_ERR_CONTINUATION = 4,
+    GEVWS_MSG_ERR_INTERLEAVE = 5,
+    GEVWS_MSG_ERR_UTF8 = 6
+};
+#define GEVWS_MSG_BEGIN 1u   /* opened in this batch */
+#define GEVWS_MSG_END   2u   /* its FIN frame is in this batch */
+
+/* What a connection carries from one pass to the next; zero = fresh. */
+typedef struct gevws_msg_state {
+    uint8_t opcode;     /* 0: no message open; 1 / 2: the open message's */
+    uint8_t failed;     /* sticky GEVWS_MSG_ERR_* */
+    uint8_t utf8_n;     /* 0..3 bytes of an unfinished sequence at the end of the open text message */
+    uint8_t utf8[3];
+    uint8_t reserved[2];
+} gevws_msg_state;
+
+/* One message: the data frames (opcode 1 / 2 and its continuations) from
+ * first_frame on that map to it in d_msg_of.  A single-frame message's payload
+ * is its frame's; a fragmented one's stays in its frames' slots. */
+typedef struct gevws_message {
+    uint64_t first_frame;   /* record index of its first data frame in this batch */
+    uint64_t length;        /* payload bytes of its data frames in this batch */
+    uint32_t conn;
+    uint32_t nframes;       /* its data frames in this batch */
+    uint8_t opcode;         /* 1 text, 2 binary (from the carry state when continued) */
+    uint8_t flags;          /* GEVWS_MSG_BEGIN | GEVWS_MSG_END */
+    uint8_t status;         /* GEVWS_MSG_OK or GEVWS_MSG_ERR_UTF8 */
+    uint8_t reserved[5];
+} gevws_message;
+
+typedef struct gevws_conn_msg {
+    uint64_t first_message;
+    uint64_t error_frame;   /* record index, or UINT64_MAX */
+    uint32_t nmessages;
+    int32_t error;          /* GEVWS_MSG_OK or the first GEVWS_MSG_ERR_* */
+    uint64_t reserved;
+} gevws_conn_msg;
+
+/* d_frames / d_conn_out / d_decoded / d_payload: a decode's records,
+ * per-connection table, summary and payload arena (the frame count is read on
+ * the device from d_decoded, none if that decode failed; max_frames bounds the
+ * launch, the scratch and d_msg_of; at most 2^32 - 1).  Every payload starts
+ * on GEVWS_PAYLOAD_ALIGN and is read as whole 16-byte vectors, but only
+ * hdr.length bytes of it count: the pad is never relied on.
+ *
+ * d_messages receives one record per message with at least one data frame in
+ * this batch, ordered by connection, then stream order -- a message continued
+ * from the carry state has no BEGIN flag and the state's opcode, one still
+ * open after the connection's last frame has no END flag (the state carries
+ * the rest).  d_msg_of[f] = the message of data frame f, -1 for every other
+ * frame (valid control frames between fragments belong to no message).
+ * d_conn_msg[c]: the connection's messages and its verdict.
+ *
+ * After a failure: on errors 1-5 the failing frame and every later frame of
+ * the connection map to no message, and an open message is emitted as it
+ * stood (no END, status OK); on a UTF-8 error the open message is emitted
+ * with status GEVWS_MSG_ERR_UTF8, counting frames and bytes up to and
+ * including the failing frame, without END, and the later frames map to no
+ * message.  The error is sticky in the state: a connection that comes in
+ * failed yields no messages and reports that error with error_frame ==
+ * UINT64_MAX.  Connections with status < 0 or no frames yield nothing, report
+ * what their state holds the same way, and keep their state.
+ *
+ * d_state: n_conns entries read and rewritten (NULL: every connection fresh,
+ * nothing kept).  d_summary: frames = messages emitted, payload_len = payload
+ * bytes of the text messages emitted (the bytes the UTF-8 check answers for),
+ * errors = connections that failed in this batch, status GEVWS_ERR_CAPACITY
+ * when there are more messages than max_messages -- frames then holds the
+ * count needed, d_messages / d_conn_msg are not written and d_state is left
+ * untouched, so the caller retries.  n_conns == 0, max_frames == 0, no
+ * decoded frames or a failed d_decoded give a zero summary and read none of
+ * the inputs (with connections, every d_conn_msg entry is still written: no
+ * messages, no error). */
+int gevws_messages_async(gevws_ctx *ctx, void *stream,
+                         const gevws_frame *d_frames, uint64_t max_frames,
+                         const gevws_conn_out *d_conn_out, uint32_t n_conns,
+                         const gevws_summary *d_decoded, const uint8_t *d_payload,
+                         gevws_msg_state *d_state,
+                         gevws_message *d_messages, uint64_t max_messages,
+                         int64_t *d_msg_of, gevws_conn_msg *d_conn_msg, gevws_summary *d_summary);
+
+/* unicode/utf8.Valid(p[:n]) in host memory (scalar; the rule the device pass
+ * applies per byte): 1 valid, 0 not. */
+int gevws_utf8_valid(const uint8_t *p, uint64_t n);
+
 /* Measurement helper, not on the reference path: n bytes (n % 16 == 0, d_dst
  * 16-byte aligned, d_src any alignment) copied with the unmask kernel's
  * streaming access pattern minus the XOR and frame lookup -- the achievable
