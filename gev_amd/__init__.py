@@ -25,6 +25,7 @@ import numpy as np
 from . import _abi
 from ._abi import (MSG_BEGIN, MSG_END, MSG_ERR_CONTINUATION, MSG_ERR_CONTROL, MSG_ERR_INTERLEAVE, MSG_ERR_OPCODE,
                    MSG_ERR_RSV, MSG_ERR_UTF8, MSG_OK)
+from ._abi import EXT_DEFLATE, INF_DONE, INF_PENDING, MSG_COMPRESSED, MSG_ERR_DEFLATE, MSG_ERR_TOO_BIG
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
                    SUMMARY_UNORDERED, TILE, Header)
@@ -50,7 +51,9 @@ MESSAGE_DTYPE = np.dtype([("first_frame", "<u8"), ("length", "<u8"), ("conn", "<
                           ("opcode", "u1"), ("flags", "u1"), ("status", "u1"), ("reserved", "u1", (5,))])
 CONN_MSG_DTYPE = np.dtype([("first_message", "<u8"), ("error_frame", "<u8"), ("nmessages", "<u4"),
                            ("error", "<i4"), ("reserved", "<u8")])
-assert FRAME_DTYPE.itemsize == 32 and CONN_OUT_DTYPE.itemsize == 32
+INFLATED_DTYPE = np.dtype([("out_off", "<u8"), ("length", "<u8"), ("status", "u1"), ("flags", "u1"),
+                           ("reserved", "u1", (14,))])
+assert FRAME_DTYPE.itemsize == 32 and CONN_OUT_DTYPE.itemsize == 32 and INFLATED_DTYPE.itemsize == 32
 assert MSG_STATE_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 32 and CONN_MSG_DTYPE.itemsize == 32
 assert SUMMARY_DTYPE.itemsize == 64 and SYNTH_DTYPE.itemsize == 24
 
@@ -67,6 +70,32 @@ def utf8_valid(b: bytes) -> bool:
     """gevws_utf8_valid: unicode/utf8.Valid on host bytes (the rule the device pass applies)."""
     b = bytes(b)
     return bool(lib.gevws_utf8_valid(ctypes.c_char_p(b), len(b)))
+
+
+def inflate_raw(b: bytes, cap: int) -> Tuple[int, bytes]:
+    """gevws_inflate_raw: one message's compressed payload inflated on the host
+    by the decoder the device runs; (MSG_OK / MSG_ERR_DEFLATE / MSG_ERR_TOO_BIG,
+    the bytes produced before the verdict), at most cap of them."""
+    b = bytes(b)
+    out = ctypes.create_string_buffer(max(cap, 1))
+    n = ctypes.c_uint64(0)
+    st = lib.gevws_inflate_raw(ctypes.c_char_p(b), len(b), out, cap, ctypes.byref(n))
+    if st < 0:
+        raise RuntimeError(f"gevws_inflate_raw: {status_string(st)}")
+    return st, out.raw[: n.value]
+
+
+def deflate_negotiate(value: bytes) -> bytes:
+    """gevws_deflate_negotiate: the Sec-WebSocket-Extensions answer to the first
+    permessage-deflate offer in `value` that the device inflate can serve
+    (no context takeover), b"" when there is none."""
+    value = bytes(value)
+    out = ctypes.create_string_buffer(256)
+    n = ctypes.c_uint64(0)
+    st = lib.gevws_deflate_negotiate(ctypes.c_char_p(value), len(value), out, len(out), ctypes.byref(n))
+    if st != OK:
+        raise RuntimeError(f"gevws_deflate_negotiate: {status_string(st)}")
+    return out.raw[: n.value]
 
 
 def _torch():
@@ -133,6 +162,27 @@ class Messages:
         if self.state is None:
             return None
         return self.state[: self.n_conns].cpu().numpy().reshape(-1).view(MSG_STATE_DTYPE)
+
+
+@dataclass
+class Inflated:
+    """Device-resident result of one inflate step (Engine.inflate)."""
+    inflated: "object"    # uint8 [n_messages, 32]   (gevws_inflated records)
+    out: "object"         # uint8 [out_cap]          (the inflated messages, each on a 16-byte boundary)
+    summary: "object"     # uint8 [64]               (gevws_summary)
+    n_messages: int
+
+    def summary_host(self) -> np.ndarray:
+        return self.summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
+
+    def inflated_host(self) -> np.ndarray:
+        return self.inflated[: self.n_messages].cpu().numpy().reshape(-1).view(INFLATED_DTYPE)
+
+    def message_bytes(self, i: int) -> bytes:
+        """The inflated bytes of message i (b"" when it has none)."""
+        r = self.inflated_host()[i]
+        off, n = int(r["out_off"]), int(r["length"])
+        return self.out[off: off + n].cpu().numpy().tobytes() if n else b""
 
 
 class _DevAddr:
@@ -446,11 +496,66 @@ class Engine:
         if st != OK:
             raise RuntimeError(f"gevws_messages_async: {status_string(st)}")
 
-    def messages(self, out: "Batch", state=None, max_messages: Optional[int] = None, stream=None) -> "Messages":
+    def messages_ext_async(self, frames, max_frames: int, conn_out, n_conns: int, decoded, payload, state, messages,
+                           max_messages: int, msg_of, conn_msg, summary, conn_ext, stream=None) -> None:
+        """gevws_messages_ext_async: the message pass with one extension byte
+        per connection (conn_ext: uint8 [n_conns], EXT_DEFLATE, or None)."""
+        st = lib.gevws_messages_ext_async(
+            self._ctx, _stream_handle(stream), frames.data_ptr(), max_frames, conn_out.data_ptr(), n_conns,
+            decoded.data_ptr(), payload.data_ptr(), state.data_ptr() if state is not None else None,
+            messages.data_ptr(), max_messages, msg_of.data_ptr(), conn_msg.data_ptr(), summary.data_ptr(),
+            conn_ext.data_ptr() if conn_ext is not None else None)
+        if st != OK:
+            raise RuntimeError(f"gevws_messages_ext_async: {status_string(st)}")
+
+    def inflate_async(self, frames, max_frames: int, messages, max_messages: int, msg_of, msg_summary, payload,
+                      max_message_bytes: int, state, inflated, out, out_cap: int, summary, stream=None) -> None:
+        """gevws_inflate_async on device tensors: the compressed messages of a
+        message pass inflated into `out` (state: the pass's uint8 [n_conns, 8],
+        or None)."""
+        st = lib.gevws_inflate_async(
+            self._ctx, _stream_handle(stream), frames.data_ptr(), max_frames, messages.data_ptr(), max_messages,
+            msg_of.data_ptr(), msg_summary.data_ptr(), payload.data_ptr(), max_message_bytes,
+            state.data_ptr() if state is not None else None, inflated.data_ptr(), out.data_ptr(), out_cap,
+            summary.data_ptr())
+        if st != OK:
+            raise RuntimeError(f"gevws_inflate_async: {status_string(st)}")
+
+    def inflate(self, out: "Batch", msgs: "Messages", max_message_bytes: int, state=None,
+                out_cap: Optional[int] = None, stream=None) -> "Inflated":
+        """The inflate step behind Engine.messages(out, conn_ext=...): every
+        whole compressed message of the pass inflated.  Grows the output once
+        on ERR_CAPACITY (nothing is written and the state is untouched by the
+        call that did not fit)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        n = int(msgs.summary_host()["frames"])
+        if out_cap is None:
+            out_cap = 4 * int(out.summary_host()["payload_bytes"]) + 16 * n
+        for attempt in range(2):
+            res = Inflated(inflated=torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=dev),
+                           out=torch.empty(max(out_cap, 16), dtype=torch.uint8, device=dev),
+                           summary=torch.zeros(64, dtype=torch.uint8, device=dev), n_messages=n)
+            self.inflate_async(out.frames, msgs.n_frames, msgs.messages, n, msgs.msg_of, msgs.summary, out.payload,
+                               max_message_bytes, state, res.inflated, res.out, out_cap, res.summary, stream)
+            torch.cuda.synchronize(self.device)
+            s = res.summary_host()
+            if int(s["status"]) == ERR_CAPACITY and attempt == 0:
+                out_cap = int(s["payload_bytes"])
+                continue
+            if int(s["status"]) != OK:
+                raise RuntimeError(f"inflate: {status_string(int(s['status']))}")
+            return res
+        raise RuntimeError("inflate: capacity retry failed")
+
+    def messages(self, out: "Batch", state=None, max_messages: Optional[int] = None, stream=None, *,
+                 conn_ext=None) -> "Messages":
         """The message pass over a decoded batch; `state` (uint8 [n_conns, 8]
         device tensor) carries open messages from pass to pass and is updated
         in place.  Grows the message table once on ERR_CAPACITY (the state is
-        untouched by the pass that did not fit)."""
+        untouched by the pass that did not fit).  conn_ext (uint8 [n_conns]
+        device tensor of EXT_DEFLATE bytes) marks the connections that
+        negotiated permessage-deflate."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n = int(out.summary_host()["frames"]) if int(out.summary_host()["status"]) == OK else 0
@@ -462,8 +567,9 @@ class Engine:
                            conn_msg=torch.zeros((max(out.n_conns, 1), 32), dtype=torch.uint8, device=dev),
                            state=state, summary=torch.zeros(64, dtype=torch.uint8, device=dev),
                            n_conns=out.n_conns, n_frames=n)
-            self.messages_async(out.frames, n, out.conn_out, out.n_conns, out.summary, out.payload, state,
-                                res.messages, max_messages, res.msg_of, res.conn_msg, res.summary, stream)
+            self.messages_ext_async(out.frames, n, out.conn_out, out.n_conns, out.summary, out.payload, state,
+                                    res.messages, max_messages, res.msg_of, res.conn_msg, res.summary, conn_ext,
+                                    stream)
             torch.cuda.synchronize(self.device)
             s = res.summary_host()
             if int(s["status"]) == ERR_CAPACITY and attempt == 0:

@@ -63,6 +63,13 @@ MSG_ERR_INTERLEAVE = 5
 MSG_ERR_UTF8 = 6
 MSG_BEGIN = 1
 MSG_END = 2
+# permessage-deflate (gevws_messages_ext_async, gevws_inflate_async)
+MSG_ERR_DEFLATE = 7
+MSG_ERR_TOO_BIG = 8
+MSG_COMPRESSED = 4
+EXT_DEFLATE = 1
+INF_DONE = 1
+INF_PENDING = 2
 
 IN_PAD = 64
 MEM_DEFAULT, MEM_FINE, MEM_UNCACHED = 0, 1, 2  # gevws_device_alloc kinds
@@ -148,6 +155,12 @@ class ConnMsg(ctypes.Structure):
                 ("nmessages", ctypes.c_uint32), ("error", ctypes.c_int32), ("reserved", ctypes.c_uint64)]
 
 
+class Inflated(ctypes.Structure):
+    """gevws_inflated: what the inflate step made of one message."""
+    _fields_ = [("out_off", ctypes.c_uint64), ("length", ctypes.c_uint64), ("status", ctypes.c_uint8),
+                ("flags", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 14)]
+
+
 class Reject(ctypes.Structure):
     """gevws_reject: RejectConnectionError options (ws/errors.go:81-129)."""
     _fields_ = [("code", ctypes.c_int32), ("plain", ctypes.c_int32), ("reason", ctypes.c_void_p),
@@ -193,6 +206,7 @@ assert ctypes.sizeof(Header) == 16 and ctypes.sizeof(Frame) == 32
 assert ctypes.sizeof(ConnIn) == 16 and ctypes.sizeof(ConnOut) == 32
 assert ctypes.sizeof(Summary) == 64 and ctypes.sizeof(SynthDesc) == 24
 assert ctypes.sizeof(MsgState) == 8 and ctypes.sizeof(Message) == 32 and ctypes.sizeof(ConnMsg) == 32
+assert ctypes.sizeof(Inflated) == 32
 
 P = ctypes.c_void_p
 U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -240,6 +254,13 @@ SIGNATURES = {
     "gevws_messages_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint32, P, P, P, P,
                                             ctypes.c_uint64, P, P, P]),
     "gevws_utf8_valid": (ctypes.c_int, [P, ctypes.c_uint64]),
+    "gevws_messages_ext_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint32, P, P, P, P,
+                                                ctypes.c_uint64, P, P, P, P]),
+    "gevws_inflate_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, P, P, P, ctypes.c_uint64, P,
+                                           P, P, ctypes.c_uint64, P]),
+    "gevws_inflate_raw": (ctypes.c_int, [P, ctypes.c_uint64, P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "gevws_deflate_negotiate": (ctypes.c_int, [P, ctypes.c_uint64, P, ctypes.c_uint64,
+                                               ctypes.POINTER(ctypes.c_uint64)]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),
     "gevws_synth_async": (ctypes.c_int, [P, P, P, P, ctypes.c_uint64, ctypes.c_uint64]),
     "gevws_synth_verify_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P,

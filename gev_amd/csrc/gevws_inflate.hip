@@ -1,0 +1,410 @@
+// gevws_inflate.hip -- permessage-deflate (RFC 7692) behind the message pass:
+// gevws_inflate_async (include/gevws.h) inflates the compressed messages of a
+// batch, one wave per message, with the block decoder of
+// gevws_inflate_core.hpp.  The reference has no code for it.
+//
+// Five launches behind one memset, no host round trip:
+//   k_inf_size     one wave per message: decodes without storing -- every
+//                  verdict but UTF-8, and the inflated length
+//   k_scan_blocks  lays the messages out in d_out, the summary, CAPACITY
+//   k_inf_emit     one wave per message: decodes again through a 32 KiB LDS
+//                  window that is flushed to d_out as 16-byte vectors; writes
+//                  d_inflated
+//   k_inf_utf8     one wave per inflated text message: the 16-byte-vector rule
+//                  of gevws_utf8.hpp over the finished output
+//   k_inf_state    one lane per connection's first message: d_state.failed
+//
+// A wave's decode state -- bit buffer, counters, each Huffman code's limits --
+// is the same in every lane; the lanes differ only where bytes move: the 1 KiB
+// refills of the input (hopping from fragment to fragment), match copies,
+// stored blocks, the window flush, and placing a block's symbols.  One wave is one workgroup, so four messages a CU hold
+// 4 x (32 KiB window + 1 KiB input + 1 KiB tables) of its 160 KiB LDS.  A
+// wave's LDS accesses complete in order, so the lanes hand bytes to each other
+// through LDS without a barrier.
+#include "gevws_inflate_core.hpp"
+#include "gevws_internal.hpp"
+#include "gevws_utf8.hpp"
+
+namespace {
+
+constexpr uint32_t kInfWin = 32768, kInfIn = 1024, kInfBlock = 64;
+static_assert(kInfIn == kInfBlock * 16, "a refill / a flush = one 16-byte vector a lane");
+
+// Keeps the compiler from moving one lane's LDS access across another's.
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+struct InfRec {  // per message, between the passes
+  uint32_t len;
+  uint8_t status, flags;
+  uint16_t pad;
+};
+static_assert(sizeof(InfRec) == 8 && sizeof(gevws_inflated) == 32, "inflate layouts");
+
+struct InfScratch {
+  uint64_t* blk;  // per message: [1 if OK, bytes of d_out, length, 1 if failed]
+  InfRec* rec;
+  size_t total;
+};
+inline InfScratch inf_scratch(void* base, uint64_t max_messages) {
+  auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+  uint8_t* p = static_cast<uint8_t*>(base);
+  InfScratch s;
+  size_t o = 0;
+  s.blk = reinterpret_cast<uint64_t*>(p + o), o += up(max_messages * kBlkFields * sizeof(uint64_t));
+  s.rec = reinterpret_cast<InfRec*>(p + o), o += up(max_messages * sizeof(InfRec));
+  s.total = o;
+  return s;
+}
+
+// ------------------------------------------------------------------ the source
+// S of message m: the payloads of its data frames, then 00 00 ff ff, through a
+// 1 KiB LDS buffer.  Reads hdr.length bytes of a frame and not one more.
+struct InfSource {
+  const gevws_frame* __restrict__ fr;
+  const int64_t* __restrict__ msg_of;
+  const uint8_t* __restrict__ payload;
+  uint8_t* inbuf;
+  uint64_t m, f, max_frames;
+  uint32_t frames_left;          // data frames of the message not opened yet
+  const uint8_t* p = nullptr;    // the open fragment: L bytes, foff of them taken
+  uint64_t L = 0, foff = 0;
+  uint32_t rd = 0, n = 0;        // the buffer holds n bytes, rd of them taken
+  uint64_t cache = 0;            // ... the last up to eight of those not handed out yet: a byte costs
+  uint32_t cache_n = 0;          //     a shift, not an LDS round trip
+  uint32_t tail_done = 0;
+  uint32_t lane;
+
+  __device__ InfSource(const gevws_frame* fr_, const int64_t* msg_of_, const uint8_t* payload_, uint8_t* inbuf_,
+                       uint64_t m_, const gevws_message& msg, uint64_t max_frames_)
+      : fr(fr_), msg_of(msg_of_), payload(payload_), inbuf(inbuf_), m(m_), f(msg.first_frame),
+        max_frames(max_frames_), frames_left(msg.nframes), lane(threadIdx.x & 63) {}
+
+  // The buffer is empty and the fragment used up: opens the next fragment
+  // with bytes, or puts the tail into the buffer; false at the end of S.
+  __device__ __forceinline__ bool advance() {
+    while (frames_left && f < max_frames) {
+      const uint64_t cur = f++;
+      if (uniform64((uint64_t)msg_of[cur]) != m) continue;  // a control frame in between
+      --frames_left;
+      const gevws_frame rec = fr[cur];
+      const int64_t len = (int64_t)uniform64((uint64_t)rec.hdr.length);
+      if (len <= 0) continue;
+      p = payload + uniform64(rec.payload_off);
+      L = (uint64_t)len;
+      foff = 0;
+      return true;
+    }
+    frames_left = 0;
+    if (tail_done) return false;
+    tail_done = 1;
+    if (lane < 4) inbuf[lane] = lane < 2 ? 0x00 : 0xff;
+    wave_lds_order();
+    rd = 0, n = 4;
+    return true;
+  }
+  __device__ __forceinline__ bool fill() {
+    if (foff == L) {
+      if (!advance()) return false;
+      if (rd < n) return true;  // the tail
+    }
+    const uint64_t left = L - foff;
+    const uint32_t k = left < kInfIn ? (uint32_t)left : kInfIn;
+    const uint32_t o = 16 * lane;
+    if (o + 16 <= k) {
+      *reinterpret_cast<u32x4*>(inbuf + o) = ld16u(p + foff + o);
+    } else {
+      for (uint32_t i = o; i < k; ++i) inbuf[i] = p[foff + i];
+    }
+    wave_lds_order();
+    foff += k;
+    rd = 0, n = k;
+    return true;
+  }
+  __device__ __forceinline__ bool get(uint32_t& b) {
+    if (cache_n == 0) {
+      if (rd == n && !fill()) return false;
+      if ((rd & 7) == 0 && n - rd >= 8) {
+        cache = uniform64(*reinterpret_cast<const uint64_t*>(inbuf + rd));
+        cache_n = 8, rd += 8;
+      } else {
+        cache = uniform32(inbuf[rd]);
+        cache_n = 1, rd += 1;
+      }
+    }
+    b = (uint32_t)(cache & 0xff);
+    cache >>= 8;
+    --cache_n;
+    return true;
+  }
+  // Up to `want` bytes passed over unread (the sizing pass's stored blocks).
+  __device__ __forceinline__ uint64_t skip(uint64_t want) {
+    uint64_t got = 0;
+    while (got < want && cache_n) cache >>= 8, --cache_n, ++got;
+    while (got < want) {
+      if (rd < n) {
+        const uint64_t k = want - got < n - rd ? want - got : n - rd;
+        rd += (uint32_t)k, got += k;
+      } else if (foff < L) {
+        const uint64_t k = want - got < L - foff ? want - got : L - foff;
+        foff += k, got += k;
+      } else if (!advance()) {
+        break;
+      }
+    }
+    return got;
+  }
+};
+
+// ------------------------------------------------------------------ the two sinks
+struct InfSizeIo : InfSource {  // counts only: the core keeps the count
+  using InfSource::InfSource;
+  __device__ __forceinline__ void put(uint32_t) {}
+  __device__ __forceinline__ void copy(uint32_t, uint32_t) {}
+  __device__ __forceinline__ uint64_t stored(uint64_t want) { return skip(want); }
+};
+
+struct InfEmitIo : InfSource {
+  uint8_t* win;  // LDS, kInfWin bytes: byte i of the output at win[i % kInfWin]
+  uint8_t* out;  // the message's bytes in d_out (16-byte aligned)
+  uint64_t pos = 0, flushed = 0;
+
+  __device__ InfEmitIo(const gevws_frame* fr_, const int64_t* msg_of_, const uint8_t* payload_, uint8_t* inbuf_,
+                       uint64_t m_, const gevws_message& msg, uint64_t max_frames_, uint8_t* win_, uint8_t* out_)
+      : InfSource(fr_, msg_of_, payload_, inbuf_, m_, msg, max_frames_), win(win_), out(out_) {}
+
+  // Whole KiB of the window to d_out.  At most 1 023 + 1 024 bytes are ever
+  // unflushed, so nothing unflushed is overwritten 32 KiB later.
+  __device__ __forceinline__ void flush() {
+    while (pos - flushed >= kInfIn) {
+      const u32x4 v = *reinterpret_cast<const u32x4*>(win + ((flushed + 16 * lane) & (kInfWin - 1)));
+      *reinterpret_cast<u32x4*>(out + flushed + 16 * lane) = v;
+      flushed += kInfIn;
+    }
+  }
+  // The rest, the last vector's pad zeroed.
+  __device__ __forceinline__ void finish() {
+    flush();
+    const uint64_t r = pos - flushed, o = 16 * (uint64_t)lane;
+    if (o < r) {
+      u32x4 v = *reinterpret_cast<const u32x4*>(win + ((flushed + o) & (kInfWin - 1)));
+      if (r - o < 16) v = keep_bytes(v, (int64_t)(r - o));
+      *reinterpret_cast<u32x4*>(out + flushed + o) = v;
+    }
+  }
+  __device__ __forceinline__ void put(uint32_t b) {
+    if (lane == 0) win[pos & (kInfWin - 1)] = (uint8_t)b;
+    wave_lds_order();
+    ++pos;
+    flush();
+  }
+  // n <= 258 bytes from d <= 32 768 back, as a byte-serial copy: byte i comes
+  // from byte i mod d of the d bytes before pos, all written before this call.
+  // A slot that byte i takes over (d + i - j = 32 768) held source byte
+  // j <= i, read in the same or an earlier round.
+  __device__ __forceinline__ void copy(uint32_t d, uint32_t len) {
+    for (uint32_t i0 = 0; i0 < len; i0 += kInfBlock) {
+      const uint32_t i = i0 + lane;
+      if (i < len) {
+        const uint32_t j = i < d ? i : i % d;
+        const uint8_t c = win[(pos - d + j) & (kInfWin - 1)];
+        win[(pos + i) & (kInfWin - 1)] = c;
+      }
+      wave_lds_order();
+    }
+    pos += len;
+    flush();
+  }
+  __device__ __forceinline__ uint64_t stored(uint64_t want) {
+    uint64_t got = 0;
+    while (got < want && cache_n) {
+      uint32_t b;
+      get(b), put(b), ++got;
+    }
+    while (got < want) {
+      if (rd == n && !fill()) break;
+      const uint32_t k = want - got < n - rd ? (uint32_t)(want - got) : n - rd;
+      for (uint32_t i = lane; i < k; i += kInfBlock) win[(pos + i) & (kInfWin - 1)] = inbuf[rd + i];
+      wave_lds_order();
+      rd += k, got += k, pos += k;
+      flush();
+    }
+    return got;
+  }
+};
+
+__device__ __forceinline__ bool inf_wanted(const gevws_message& msg) {
+  const uint32_t all = GEVWS_MSG_COMPRESSED | GEVWS_MSG_BEGIN | GEVWS_MSG_END;
+  return (msg.flags & all) == all;
+}
+
+// ------------------------------------------------------------------ 1. sizes and verdicts
+__global__ __launch_bounds__(kInfBlock) void k_inf_size(const gevws_frame* __restrict__ fr, uint64_t max_frames,
+                                                        const gevws_message* __restrict__ msgs,
+                                                        uint64_t max_messages, const int64_t* __restrict__ msg_of,
+                                                        const gevws_summary* __restrict__ gate,
+                                                        const uint8_t* __restrict__ payload, uint64_t limit,
+                                                        uint64_t* __restrict__ blk, InfRec* __restrict__ rec) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_in[kInfIn];
+  __shared__ gevws_inflate::Tables s_tab;
+  const uint64_t m = blockIdx.x;
+  if (m >= gated_count(max_messages, gate)) return;  // (blk and rec are zeroed)
+  const gevws_message msg = msgs[m];
+  if (!(msg.flags & GEVWS_MSG_COMPRESSED)) return;
+  InfRec r;
+  r.len = 0, r.status = GEVWS_MSG_OK, r.flags = GEVWS_INF_PENDING, r.pad = 0;
+  uint64_t len = 0;
+  if (inf_wanted(msg)) {
+    InfSizeIo io(fr, msg_of, payload, s_in, m, msg, max_frames);
+    r.status = (uint8_t)gevws_inflate::inflate(io, s_tab, limit, &len);
+    r.flags = GEVWS_INF_DONE;
+    if (r.status != GEVWS_MSG_OK) len = 0;
+    r.len = (uint32_t)len;
+  }
+  if (threadIdx.x == 0) {
+    rec[m] = r;
+    if (r.flags == GEVWS_INF_DONE) {
+      const bool ok = r.status == GEVWS_MSG_OK;
+      blk[m * kBlkFields + 0] = ok ? 1 : 0;
+      blk[m * kBlkFields + 1] = round16(len);
+      blk[m * kBlkFields + 2] = len;
+      blk[m * kBlkFields + 3] = ok ? 0 : 1;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ 2. the bytes
+__global__ __launch_bounds__(kInfBlock) void k_inf_emit(const gevws_frame* __restrict__ fr, uint64_t max_frames,
+                                                        const gevws_message* __restrict__ msgs,
+                                                        uint64_t max_messages, const int64_t* __restrict__ msg_of,
+                                                        const gevws_summary* __restrict__ gate,
+                                                        const uint8_t* __restrict__ payload,
+                                                        const uint64_t* __restrict__ blk,
+                                                        const InfRec* __restrict__ rec,
+                                                        const gevws_summary* __restrict__ sum,
+                                                        gevws_inflated* __restrict__ inflated,
+                                                        uint8_t* __restrict__ d_out) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_win[kInfWin];
+  __shared__ __attribute__((aligned(16))) uint8_t s_in[kInfIn];
+  __shared__ gevws_inflate::Tables s_tab;
+  if (sum->status != GEVWS_OK) return;  // capacity: nothing written
+  const uint64_t m = blockIdx.x;
+  if (m >= gated_count(max_messages, gate)) return;
+  const InfRec r = rec[m];
+  const uint64_t base = blk[m * kBlkFields + 1];  // (exclusive after the scan)
+  if (threadIdx.x == 0) {
+    gevws_inflated o;
+    memset(&o, 0, sizeof(o));
+    if (r.flags) {
+      o.out_off = r.flags == GEVWS_INF_DONE ? base : 0;
+      o.length = r.len;
+      o.status = r.status;
+      o.flags = r.flags;
+    }
+    inflated[m] = o;
+  }
+  if (r.flags != GEVWS_INF_DONE || r.status != GEVWS_MSG_OK || r.len == 0) return;
+  const gevws_message msg = msgs[m];
+  InfEmitIo io(fr, msg_of, payload, s_in, m, msg, max_frames, s_win, d_out + base);
+  uint64_t len = 0;
+  // the sized length is the limit: the wave never writes past its allotted bytes
+  (void)gevws_inflate::inflate(io, s_tab, (uint64_t)r.len, &len);
+  io.finish();
+}
+
+// ------------------------------------------------------------------ 3. inflated text is UTF-8
+__global__ __launch_bounds__(kWalkBlock) void k_inf_utf8(const gevws_message* __restrict__ msgs, uint64_t max_messages,
+                                                         const gevws_summary* __restrict__ gate,
+                                                         gevws_summary* __restrict__ sum,
+                                                         gevws_inflated* __restrict__ inflated,
+                                                         const uint8_t* __restrict__ d_out) {
+  if (sum->status != GEVWS_OK) return;
+  const uint64_t m = (uint64_t)blockIdx.x * (kWalkBlock / 64) + (threadIdx.x >> 6);  // one wave per message
+  if (m >= gated_count(max_messages, gate)) return;
+  const gevws_inflated o = inflated[m];
+  if (o.flags != GEVWS_INF_DONE || o.status != GEVWS_MSG_OK || o.length == 0 || msgs[m].opcode != 1) return;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint8_t* __restrict__ p = d_out + o.out_off;
+  const uint64_t L = o.length, nvec = (L + 15) >> 4;
+  uint32_t bad = 0;
+  for (uint64_t j = lane; j < nvec; j += 64) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(p + 16 * j);
+    const uint32_t pw = j ? *reinterpret_cast<const uint32_t*>(p + 16 * j - 4) : 0u;
+    bad |= utf8_vec_bad(v, pw, j, L, 0);
+  }
+  // ... and the text does not end inside a sequence
+  const uint32_t l1 = p[L - 1], l2 = L >= 2 ? p[L - 2] : 0u, l3 = L >= 3 ? p[L - 3] : 0u;
+  bad |= (uint32_t)(l1 >= 0xC0 || l2 >= 0xE0 || l3 >= 0xF0);
+  if (__ballot(bad != 0) != 0 && lane == 0) {
+    inflated[m].status = GEVWS_MSG_ERR_UTF8;
+    atomicAdd(reinterpret_cast<unsigned long long*>(&sum->frames), ~0ull);  // one OK message fewer
+    atomicAdd(reinterpret_cast<unsigned long long*>(&sum->errors), 1ull);
+  }
+}
+
+// ------------------------------------------------------------------ 4. the carry state
+__global__ __launch_bounds__(kWalkBlock) void k_inf_state(const gevws_message* __restrict__ msgs,
+                                                          uint64_t max_messages,
+                                                          const gevws_summary* __restrict__ gate,
+                                                          const gevws_summary* __restrict__ sum,
+                                                          const gevws_inflated* __restrict__ inflated,
+                                                          gevws_msg_state* __restrict__ state) {
+  if (sum->status != GEVWS_OK) return;  // capacity: the state kept for the retry
+  const uint64_t n = gated_count(max_messages, gate);
+  const uint64_t m = (uint64_t)blockIdx.x * kWalkBlock + threadIdx.x;
+  if (m >= n) return;
+  const uint32_t c = msgs[m].conn;
+  if (m && msgs[m - 1].conn == c) return;  // the connection's first message walks its messages
+  for (uint64_t k = m; k < n && msgs[k].conn == c; ++k) {
+    const gevws_inflated o = inflated[k];
+    if (o.flags == GEVWS_INF_DONE && o.status != GEVWS_MSG_OK) {
+      if (state[c].failed == 0) state[c].failed = o.status;
+      break;
+    }
+  }
+}
+
+}  // namespace
+
+using namespace gevws_impl;
+
+extern "C" int gevws_inflate_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames, uint64_t max_frames,
+                                   const gevws_message* d_messages, uint64_t max_messages, const int64_t* d_msg_of,
+                                   const gevws_summary* d_msg_summary, const uint8_t* d_payload,
+                                   uint64_t max_message_bytes, gevws_msg_state* d_state,
+                                   gevws_inflated* d_inflated, uint8_t* d_out, uint64_t out_cap,
+                                   gevws_summary* d_summary) {
+  if (!ctx || !d_summary || max_messages > 0x7FFFFFFFull || max_message_bytes < 1 ||
+      max_message_bytes > 0xFFFFFFFFull)
+    return GEVWS_ERR_INVALID;
+  DeviceGuard g(ctx->device);
+  hipStream_t st = pick_stream(ctx, stream);
+  if (max_messages == 0 || max_frames == 0) {
+    GEVWS_HIP(hipMemsetAsync(d_summary, 0, sizeof(gevws_summary), st));
+    return GEVWS_OK;
+  }
+  if (!d_frames || !d_messages || !d_msg_of || !d_msg_summary || !d_payload || !d_inflated || (out_cap && !d_out))
+    return GEVWS_ERR_INVALID;
+  int r = order_after_last(ctx, st);
+  if (r != GEVWS_OK) return r;
+  r = ensure_scratch(ctx, inf_scratch(nullptr, max_messages).total);
+  if (r != GEVWS_OK) return r;
+  const InfScratch s = inf_scratch(ctx->scratch, max_messages);
+  GEVWS_HIP(hipMemsetAsync(ctx->scratch, 0, s.total, st));
+  const uint32_t nm = (uint32_t)max_messages;
+  k_inf_size<<<nm, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of, d_msg_summary,
+                                       d_payload, max_message_bytes, s.blk, s.rec);
+  k_scan_blocks<false><<<1, kScanBlock, 0, st>>>(s.blk, nm, UINT64_MAX, out_cap, d_summary);
+  k_inf_emit<<<nm, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of, d_msg_summary,
+                                       d_payload, s.blk, s.rec, d_summary, d_inflated, d_out);
+  k_inf_utf8<<<(nm + kWalkBlock / 64 - 1) / (kWalkBlock / 64), kWalkBlock, 0, st>>>(d_messages, max_messages,
+                                                                                   d_msg_summary, d_summary,
+                                                                                   d_inflated, d_out);
+  if (d_state)
+    k_inf_state<<<(nm + kWalkBlock - 1) / kWalkBlock, kWalkBlock, 0, st>>>(d_messages, max_messages, d_msg_summary,
+                                                                           d_summary, d_inflated, d_state);
+  GEVWS_HIP(hipGetLastError());
+  return mark_last(ctx, st);
+}

@@ -19,65 +19,21 @@
 //                      d_conn_msg, d_state
 // Only the UTF-8 pass touches payload bytes (every byte of every text frame,
 // once); the other passes read records and one byte / word per frame.
+// gevws_messages_ext_async adds one extension byte per connection: on a
+// permessage-deflate connection RSV1 on an opcode-1 / 2 frame opens a
+// compressed message, whose frames get the class bit kClsComp and skip the
+// UTF-8 pass (gevws_inflate.hip inflates them and checks the text afterwards).
 #include "gevws_internal.hpp"
+#include "gevws_utf8.hpp"
 
 namespace {
-
-// ------------------------------------------------------------------ the UTF-8 rule
-// Whether byte c is wrong after the bytes p3 p2 p1 (0 before the start): a
-// byte is a continuation (10xxxxxx) exactly when a lead byte one, two or three
-// places back still asks for one; C0, C1 and F5..FF never appear; and the byte
-// after E0 / ED / F0 / F4 stays in the narrowed range (no overlong forms, no
-// surrogates, nothing above U+10FFFF).  unicode/utf8.Valid accepts exactly the
-// strings with no wrong byte that do not end inside a sequence.
-__host__ __device__ __forceinline__ uint32_t utf8_byte_bad(uint32_t c, uint32_t p1, uint32_t p2, uint32_t p3) {
-  const bool must = p1 >= 0xC0 || p2 >= 0xE0 || p3 >= 0xF0;
-  const bool cont = (c & 0xC0) == 0x80;
-  return (uint32_t)((must != cont) || c == 0xC0 || c == 0xC1 || c >= 0xF5 || (p1 == 0xE0 && c < 0xA0) ||
-                    (p1 == 0xED && c > 0x9F) || (p1 == 0xF0 && c < 0x90) || (p1 == 0xF4 && c > 0x8F));
-}
-// Continuation bytes a lead byte asks for.
-__host__ __device__ __forceinline__ uint32_t utf8_need(uint32_t c) {
-  return (uint32_t)(c >= 0xC0) + (uint32_t)(c >= 0xE0) + (uint32_t)(c >= 0xF0);
-}
-
-// Bit i = byte i of the vector v is wrong; prevw = the four bytes before it.
-// A vector of ASCII can only be wrong in its first three bytes, after an
-// unfinished sequence.
-__device__ __forceinline__ uint32_t utf8_err16(u32x4 v, uint32_t prevw) {
-  uint32_t p1 = prevw >> 24, p2 = (prevw >> 16) & 0xff, p3 = (prevw >> 8) & 0xff;
-  if (((v[0] | v[1] | v[2] | v[3]) & 0x80808080u) == 0)
-    return (uint32_t)(p1 >= 0xC0 || p2 >= 0xE0 || p3 >= 0xF0) | ((uint32_t)(p1 >= 0xE0 || p2 >= 0xF0) << 1) |
-           ((uint32_t)(p1 >= 0xF0) << 2);
-  uint32_t err = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const uint32_t c = (v[w] >> (8 * b)) & 0xff;
-      err |= utf8_byte_bad(c, p1, p2, p3) << (4 * w + b);
-      p3 = p2;
-      p2 = p1;
-      p1 = c;
-    }
-  }
-  return err;
-}
-
-// Wrong bytes among [lead, L) of vector j of the frame at p (16-byte aligned):
-// the leading continuation bytes belong to the previous fragment's sequence
-// and the bytes from L on are pad.
-__device__ __forceinline__ uint32_t utf8_vec_bad(u32x4 v, uint32_t prevw, uint64_t j, uint64_t L, uint32_t lead) {
-  const uint64_t left = L - 16 * j;
-  uint32_t mask = left >= 16 ? 0xffffu : ((1u << (uint32_t)left) - 1u);
-  if (j == 0) mask &= ~((1u << lead) - 1u);
-  return utf8_err16(v, prevw) & mask;
-}
 
 // ------------------------------------------------------------------ scratch
 // cls[f]: what frame f is to the message layer (0: control frame, or past its
 // connection's frame-level error, or not looked at)
 constexpr uint32_t kClsData = 1, kClsText = 2, kClsBegin = 4, kClsEnd = 8;
+// a data frame of a compressed message (permessage-deflate): its bytes are DEFLATE, not text
+constexpr uint32_t kClsComp = 16;
 // part[f] of a text-message data frame: bits 0-2 `lead`, its leading
 // continuation bytes (4 = four or more); bits 3-4 `tail`, the bytes of the
 // unfinished sequence at its end; bit 5 `bad`, a wrong byte in [lead, L)
@@ -101,7 +57,7 @@ struct MsgConn {  // per-connection hand-off between the passes (32 bytes)
   uint32_t nmsg;
   gevws_msg_state st;  // classify: the state the connection came in with; stitch: the one it leaves with
   uint32_t active;     // its frames are walked (status OK, has frames, not failed before)
-  uint32_t pad;
+  uint32_t ext;        // its GEVWS_EXT_* bits (d_conn_ext)
 };
 static_assert(sizeof(MsgConn) == 32 && sizeof(gevws_msg_state) == 8 && sizeof(gevws_message) == 32 &&
                   sizeof(gevws_conn_msg) == 32, "message-layer layouts");
@@ -136,6 +92,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_msg_classify(const gevws_frame* 
                                                              const gevws_conn_out* __restrict__ cout, uint32_t n_conns,
                                                              const gevws_summary* __restrict__ gate,
                                                              const gevws_msg_state* __restrict__ state,
+                                                             const uint8_t* __restrict__ conn_ext,
                                                              uint8_t* __restrict__ cls, MsgConn* __restrict__ work) {
   const uint64_t n = gated_count(max_frames, gate);
   const uint32_t c = blockIdx.x * kWalkBlock + threadIdx.x;
@@ -146,12 +103,15 @@ __global__ __launch_bounds__(kWalkBlock) void k_msg_classify(const gevws_frame* 
   if (n) {  // (a pass without frames reads none of its inputs)
     const gevws_conn_out co = cout[c];
     if (state) w.st = state[c];
+    if (conn_ext) w.ext = conn_ext[c] & GEVWS_EXT_DEFLATE;
     w.err = w.st.failed;
     const uint64_t first = co.first_frame;
     const uint64_t end = first < n ? (co.nframes < n - first ? first + co.nframes : n) : first;
     if (co.status == GEVWS_OK && end > first && !w.st.failed) {
       w.active = 1;
       uint32_t open = w.st.opcode == 1 || w.st.opcode == 2 ? w.st.opcode : 0u;
+      const bool deflate = w.ext != 0;
+      bool comp = deflate && open && w.st.reserved[0];  // the open message is compressed
       bool done = false;
       for (uint64_t f0 = first; f0 < end && !done; f0 += kMsgWalkBatch) {
         gevws_header hb[kMsgWalkBatch];
@@ -165,7 +125,8 @@ __global__ __launch_bounds__(kWalkBlock) void k_msg_classify(const gevws_frame* 
           const gevws_header h = hb[u];
           const uint32_t op = h.opcode;
           int e = GEVWS_MSG_OK;
-          if (h.rsv) e = GEVWS_MSG_ERR_RSV;
+          // RSV1 belongs to a deflate connection's first data frames only (RFC 7692 section 6)
+          if (deflate ? ((h.rsv & 3) || ((h.rsv & 4) && ((op & 8) || op == 0))) : h.rsv != 0) e = GEVWS_MSG_ERR_RSV;
           else if (op > 0xA || (op > 2 && op < 8)) e = GEVWS_MSG_ERR_OPCODE;
           else if ((op & 8) && (!h.fin || (uint64_t)h.length > 125)) e = GEVWS_MSG_ERR_CONTROL;
           else if (op == 0 && !open) e = GEVWS_MSG_ERR_CONTINUATION;
@@ -177,8 +138,9 @@ __global__ __launch_bounds__(kWalkBlock) void k_msg_classify(const gevws_frame* 
             break;
           }
           if (op & 8) continue;
-          if (op) open = op;
-          cls[f] = (uint8_t)(kClsData | (open == 1 ? kClsText : 0u) | (op ? kClsBegin : 0u) | (h.fin ? kClsEnd : 0u));
+          if (op) open = op, comp = (h.rsv & 4) != 0;
+          cls[f] = (uint8_t)(kClsData | (open == 1 ? kClsText : 0u) | (op ? kClsBegin : 0u) | (h.fin ? kClsEnd : 0u) |
+                             (comp ? kClsComp : 0u));
           if (h.fin) open = 0;
         }
       }
@@ -229,7 +191,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_msg_utf8_frames(const gevws_fram
   if (f >= n) return;
   const uint32_t k = cls[f];
   const gevws_frame rec = fr[f];  // (requested beside cls[f], not behind it)
-  if (!(k & kClsText)) return;
+  if (!(k & kClsText) || (k & kClsComp)) return;
   const uint64_t L = (uint64_t)rec.hdr.length;
   if (L == 0) return;  // part 0
   const uint8_t* __restrict__ p = payload + rec.payload_off;
@@ -384,7 +346,8 @@ __global__ __launch_bounds__(kWalkBlock) void k_msg_stitch(const gevws_frame* __
     const gevws_conn_out co = cout[c];
     const uint64_t first = co.first_frame, end = co.nframes < n - first ? first + co.nframes : n;
     uint32_t open = w.st.opcode == 1 || w.st.opcode == 2 ? w.st.opcode : 0u;
-    uint32_t pn = open == 1 && w.st.utf8_n <= 3 ? w.st.utf8_n : 0u;
+    bool comp = w.ext && open && w.st.reserved[0];
+    uint32_t pn = open == 1 && !comp && w.st.utf8_n <= 3 ? w.st.utf8_n : 0u;
     uint8_t pend[3] = {w.st.utf8[0], w.st.utf8[1], w.st.utf8[2]};
     bool in_batch = false;  // the open message has a data frame in this batch
     const uint64_t stop = w.err_frame < end ? w.err_frame : end;  // the frame-level error, if any
@@ -403,7 +366,8 @@ __global__ __launch_bounds__(kWalkBlock) void k_msg_stitch(const gevws_frame* __
         if (!(k & kClsData)) continue;
         if (k & kClsBegin) open = k & kClsText ? 1u : 2u;
         if ((k & kClsBegin) || !in_batch) ++nmsg, in_batch = true;
-        if (k & kClsText) {
+        comp = (k & kClsComp) != 0;
+        if ((k & kClsText) && !comp) {
           const uint64_t L = (uint64_t)recb[u].hdr.length;
           text_bytes += L;
           bool ok = L == 0 || utf8_stitch(payload + recb[u].payload_off, L, ptb[u], pend, pn);
@@ -424,7 +388,8 @@ __global__ __launch_bounds__(kWalkBlock) void k_msg_stitch(const gevws_frame* __
       failed = 1;
     } else {
       w.st.opcode = (uint8_t)open;
-      w.st.utf8_n = (uint8_t)(open == 1 ? pn : 0u);
+      w.st.utf8_n = (uint8_t)(open == 1 && !comp ? pn : 0u);
+      w.st.reserved[0] = (uint8_t)(open && comp ? 1 : 0);
       for (uint32_t i = 0; i < w.st.utf8_n; ++i) w.st.utf8[i] = pend[i];
     }
     w.nmsg = (uint32_t)nmsg;
@@ -508,7 +473,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_msg_emit(const gevws_frame* __re
         m.length = 0;
         m.nframes = 0;
         m.opcode = k & kClsText ? 1 : 2;
-        m.flags = k & kClsBegin ? GEVWS_MSG_BEGIN : 0;
+        m.flags = (uint8_t)((k & kClsBegin ? GEVWS_MSG_BEGIN : 0u) | (k & kClsComp ? GEVWS_MSG_COMPRESSED : 0u));
         m.status = GEVWS_MSG_OK;
         in_batch = true;
       }
@@ -553,6 +518,15 @@ int gevws_messages_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_fram
                          const uint8_t* d_payload, gevws_msg_state* d_state, gevws_message* d_messages,
                          uint64_t max_messages, int64_t* d_msg_of, gevws_conn_msg* d_conn_msg,
                          gevws_summary* d_summary) {
+  return gevws_messages_ext_async(ctx, stream, d_frames, max_frames, d_conn_out, n_conns, d_decoded, d_payload,
+                                  d_state, d_messages, max_messages, d_msg_of, d_conn_msg, d_summary, nullptr);
+}
+
+int gevws_messages_ext_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames, uint64_t max_frames,
+                             const gevws_conn_out* d_conn_out, uint32_t n_conns, const gevws_summary* d_decoded,
+                             const uint8_t* d_payload, gevws_msg_state* d_state, gevws_message* d_messages,
+                             uint64_t max_messages, int64_t* d_msg_of, gevws_conn_msg* d_conn_msg,
+                             gevws_summary* d_summary, const uint8_t* d_conn_ext) {
   if (!ctx || !d_summary || max_frames > 0xFFFFFFFFull) return GEVWS_ERR_INVALID;
   DeviceGuard g(ctx->device);
   hipStream_t st = pick_stream(ctx, stream);
@@ -571,8 +545,8 @@ int gevws_messages_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_fram
   const MsgScratch s = msg_scratch(ctx->scratch, max_frames, n_conns, nblk);
   GEVWS_HIP(hipMemsetAsync(s.ctl, 0, s.zero_bytes, st));
   if (max_frames) GEVWS_HIP(hipMemsetAsync(d_msg_of, 0xFF, max_frames * sizeof(int64_t), st));  // -1: no message
-  k_msg_classify<<<nblk, kWalkBlock, 0, st>>>(d_frames, max_frames, d_conn_out, n_conns, d_decoded, d_state, s.cls,
-                                              s.conn);
+  k_msg_classify<<<nblk, kWalkBlock, 0, st>>>(d_frames, max_frames, d_conn_out, n_conns, d_decoded, d_state, d_conn_ext,
+                                              s.cls, s.conn);
   const uint32_t fblk = (uint32_t)((max_frames + kWalkBlock / 64 - 1) / (kWalkBlock / 64));
   if (fblk)
     k_msg_utf8_frames<<<fblk, kWalkBlock, 0, st>>>(d_frames, max_frames, d_decoded, d_payload, s.cls, s.part, s.ctl,

@@ -642,4 +642,64 @@ void Upgrader::Upgrade(gevws_conn* conn, RingBuffer* in, HandshakeResult* r) con
   r->http_code = 101;
 }
 
+// ------------------------------------------------------------------ permessage-deflate (RFC 7692 section 7.1)
+// The answer to the first permessage-deflate offer of a Sec-WebSocket-Extensions
+// value that a server inflating without context takeover can serve, "" when
+// there is none (gevws_deflate_negotiate, include/gevws.h).
+namespace {
+// 8..15, no leading zero (RFC 7692 section 7.1.2.1)
+bool window_bits(const std::string& v, int* bits) {
+  if (v.empty() || v.size() > 2 || v[0] == '0') return false;
+  int n = 0;
+  for (char c : v) {
+    if (c < '0' || c > '9') return false;
+    n = 10 * n + (c - '0');
+  }
+  *bits = n;
+  return n >= 8 && n <= 15;
+}
+}  // namespace
+
+std::string DeflateAnswer(const uint8_t* offer, uint64_t n) {
+  std::vector<ExtOption> opts;
+  if (!scan_options(Bytes{offer, n}, &opts)) return "";
+  for (const ExtOption& o : opts) {
+    if (o.name != "permessage-deflate") continue;
+    bool ok = true, seen[4] = {false, false, false, false};
+    int server_bits = 0;
+    for (const auto& kv : o.params) {
+      const std::string& k = kv.first;
+      const bool has = kv.second.first;
+      const std::string& v = kv.second.second;
+      int which, bits = 0;
+      if (k == "server_no_context_takeover") which = 0, ok = ok && !has;
+      else if (k == "client_no_context_takeover") which = 1, ok = ok && !has;
+      else if (k == "server_max_window_bits") which = 2, ok = ok && has && window_bits(v, &server_bits);
+      else if (k == "client_max_window_bits") which = 3, ok = ok && (!has || window_bits(v, &bits));
+      else {
+        ok = false;
+        break;
+      }
+      if (seen[which]) ok = false;
+      seen[which] = true;
+    }
+    if (!ok) continue;
+    std::string a = "permessage-deflate; client_no_context_takeover; server_no_context_takeover";
+    if (seen[2]) a += "; server_max_window_bits=" + std::to_string(server_bits);
+    return a;
+  }
+  return "";
+}
+
 }  // namespace gevws
+
+extern "C" int gevws_deflate_negotiate(const uint8_t* offer, uint64_t n, uint8_t* out, uint64_t cap,
+                                       uint64_t* out_len) {
+  if (out_len) *out_len = 0;
+  if ((n && !offer) || !out_len) return GEVWS_ERR_INVALID;
+  const std::string a = gevws::DeflateAnswer(offer, n);
+  if (a.size() > cap || (a.size() && !out)) return GEVWS_ERR_CAPACITY;
+  if (!a.empty()) memcpy(out, a.data(), a.size());
+  *out_len = a.size();
+  return GEVWS_OK;
+}

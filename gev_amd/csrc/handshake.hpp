@@ -41,4 +41,8 @@ class Upgrader {
   void Upgrade(gevws_conn* conn, RingBuffer* in, HandshakeResult* r) const;
 };
 
+// The Sec-WebSocket-Extensions answer to the first permessage-deflate offer in
+// `offer` that needs no context takeover of the server; "" when there is none.
+std::string DeflateAnswer(const uint8_t* offer, uint64_t n);
+
 }  // namespace gevws

@@ -507,6 +507,109 @@ int gevws_messages_async(gevws_ctx *ctx, void *stream,
  * applies per byte): 1 valid, 0 not. */
 int gevws_utf8_valid(const uint8_t *p, uint64_t n);
 
+/* ---------------------------------------------------------------- permessage-deflate (RFC 7692)
+ * The message pass for connections that negotiated the extension, and the
+ * step that inflates their compressed messages on the device.  Additions to
+ * ABI version 3: nothing above changes.
+ *
+ * gevws_messages_ext_async is gevws_messages_async plus d_conn_ext, one byte
+ * per connection; NULL or a zero byte is the plain pass, bit for bit
+ * (gevws_messages_async is the NULL call).  For a connection with
+ * GEVWS_EXT_DEFLATE (hdr.rsv is (b0 & 0x70) >> 4, so RSV1 is 4):
+ *   - check 1 becomes: rsv & 3, or rsv & 4 on a control frame or on a
+ *     continuation frame, is GEVWS_MSG_ERR_RSV; the order of the checks stays;
+ *   - a frame with opcode 1 / 2 and RSV1 opens a compressed message: its
+ *     record carries GEVWS_MSG_COMPRESSED, and while it is open
+ *     gevws_msg_state.reserved[0] is 1 (zero: not compressed, so states
+ *     written before stay valid); a message continued from the state is
+ *     flagged from it;
+ *   - text frames of a compressed message are not UTF-8-checked (their bytes
+ *     are DEFLATE), do not count in summary.payload_len, and leave the
+ *     state's utf8 fields zero. */
+#define GEVWS_EXT_DEFLATE 1u
+#define GEVWS_MSG_COMPRESSED 4u   /* gevws_message.flags */
+int gevws_messages_ext_async(gevws_ctx *ctx, void *stream,
+                             const gevws_frame *d_frames, uint64_t max_frames,
+                             const gevws_conn_out *d_conn_out, uint32_t n_conns,
+                             const gevws_summary *d_decoded, const uint8_t *d_payload,
+                             gevws_msg_state *d_state,
+                             gevws_message *d_messages, uint64_t max_messages,
+                             int64_t *d_msg_of, gevws_conn_msg *d_conn_msg, gevws_summary *d_summary,
+                             const uint8_t *d_conn_ext);
+
+/* The inflate step, behind the message pass and on its tables.
+ *
+ * Input.  For every message with COMPRESSED | BEGIN | END the compressed
+ * stream S is the payloads of its data frames in order -- the frames f from
+ * first_frame on with d_msg_of[f] == m; control frames in between, empty
+ * fragments and the slots' padding are skipped, only hdr.length bytes of a
+ * frame are read -- followed by the four bytes 00 00 ff ff (RFC 7692 section
+ * 7.2.2).  No context takeover: every message starts with an empty window
+ * (gevws_deflate_negotiate answers offers accordingly).
+ *
+ * Verdict.  S is raw DEFLATE (RFC 1951) read from bit 0.  A block that ends
+ * with BFINAL set ends the message (the rest of S is ignored); a block that
+ * ends with no whole byte of S unread ends it as well.  Running out of S
+ * anywhere else, a distance beyond the bytes produced so far and anything
+ * zlib's inflate rejects (block type 3, stored LEN != ~NLEN, more than 286
+ * length or 30 distance codes, an over-subscribed or disallowed-incomplete
+ * code, a repeat with nothing to repeat or past the end, no end-of-block code,
+ * length symbols 286 / 287, distance symbols 30 / 31, an unassigned code) are
+ * GEVWS_MSG_ERR_DEFLATE: truncation and malformation share the code.  More
+ * than max_message_bytes (1 .. 2^32 - 1) bytes of output is
+ * GEVWS_MSG_ERR_TOO_BIG.  A text message whose inflated bytes fail
+ * gevws_utf8_valid is GEVWS_MSG_ERR_UTF8; its bytes and length are kept.
+ *
+ * Output.  d_inflated[m] belongs to d_messages[m].  The inflated messages lie
+ * in d_out in message order, each on a GEVWS_PAYLOAD_ALIGN boundary, the pad
+ * behind each zeroed; a message that failed with DEFLATE or TOO_BIG takes no
+ * space.  Compressed messages without both BEGIN and END are not touched and
+ * get GEVWS_INF_PENDING (the caller holds their input: a compressed message
+ * is inflated by the pass that sees all of it).  Messages that are not
+ * compressed get a zero record.  d_summary: frames = messages inflated with
+ * status OK, payload_bytes = bytes of d_out used, payload_len = the sum of
+ * the lengths, errors = messages that failed; status GEVWS_ERR_CAPACITY when
+ * out_cap is too small -- payload_bytes then holds the need, nothing else is
+ * written and d_state is untouched, so the caller retries.  With d_state, a
+ * connection's first failed message in batch order sets its `failed` if that
+ * was zero; its later messages are still inflated.  A failed d_msg_summary or
+ * no messages give a zero summary and read none of the inputs. */
+enum { GEVWS_MSG_ERR_DEFLATE = 7, GEVWS_MSG_ERR_TOO_BIG = 8 };   /* continue the GEVWS_MSG_* enum */
+#define GEVWS_INF_DONE 1u      /* inflated in this call (status says how it went) */
+#define GEVWS_INF_PENDING 2u   /* compressed, but not whole in this batch: not touched */
+typedef struct gevws_inflated {   /* 32 bytes */
+    uint64_t out_off;   /* into d_out, on GEVWS_PAYLOAD_ALIGN */
+    uint64_t length;    /* inflated bytes; 0 unless status is OK or ERR_UTF8 */
+    uint8_t status;     /* GEVWS_MSG_OK, _ERR_DEFLATE, _ERR_TOO_BIG, _ERR_UTF8 */
+    uint8_t flags;      /* GEVWS_INF_*; 0 for a message that is not compressed */
+    uint8_t reserved[14];
+} gevws_inflated;
+int gevws_inflate_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_frames, uint64_t max_frames,
+                        const gevws_message *d_messages, uint64_t max_messages, const int64_t *d_msg_of,
+                        const gevws_summary *d_msg_summary, const uint8_t *d_payload,
+                        uint64_t max_message_bytes, gevws_msg_state *d_state /* may be NULL */,
+                        gevws_inflated *d_inflated, uint8_t *d_out, uint64_t out_cap, gevws_summary *d_summary);
+
+/* The same decoder on host memory: in[0, n) is one message's compressed
+ * payload (the tail 00 00 ff ff is appended inside), out[0, cap) receives at
+ * most cap bytes.  Returns GEVWS_MSG_OK, GEVWS_MSG_ERR_DEFLATE or
+ * GEVWS_MSG_ERR_TOO_BIG (more than cap bytes), or GEVWS_ERR_INVALID for a
+ * NULL buffer; *out_len = the bytes written before the verdict. */
+int gevws_inflate_raw(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len);
+
+/* Answers a Sec-WebSocket-Extensions request value (offer[0, n)) for a server
+ * that inflates on the device: the first permessage-deflate offer it can
+ * serve is answered with
+ *   permessage-deflate; client_no_context_takeover; server_no_context_takeover
+ * plus "; server_max_window_bits=N" when the offer carried it (the server
+ * never compresses, so any N in 8..15 holds).  client_max_window_bits, with
+ * or without a value in 8..15, is accepted and not echoed.  An offer with an
+ * unknown parameter, a repeated one or a bad value is skipped.  *out_len = the
+ * answer's length, 0 when no offer is usable or the value is malformed.
+ * Returns GEVWS_OK, or GEVWS_ERR_CAPACITY when the answer does not fit
+ * out[0, cap).  Meant to be called from the upgrader's extension_custom hook. */
+int gevws_deflate_negotiate(const uint8_t *offer, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len);
+
 /* Measurement helper, not on the reference path: n bytes (n % 16 == 0, d_dst
  * 16-byte aligned, d_src any alignment) copied with the unmask kernel's
  * streaming access pattern minus the XOR and frame lookup -- the achievable

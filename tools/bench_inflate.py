@@ -1,0 +1,210 @@
+#!/usr/bin/env python3
+"""Measure the inflate step (gevws_inflate_async: one wave per compressed
+message) behind a decode and the message pass, beside two baselines for the
+same batch: that decode's own unmask (gevws_ctx_timing), and zlib inflating
+the same messages on this machine's CPUs, on one core and on 16 processes.
+
+Two shapes -- 16 384 connections with one 4 KiB text message each, and 1 024
+with one of 256 KiB -- times two payloads: compressible text (zlib level 6)
+and level-0 stored blocks, which is the copy bound.  Every message is one
+masked text frame with RSV1; a shape's messages cycle through eight distinct
+texts.  Decode, message pass and inflate step alternate in one process; the
+inflate step is timed by HIP events around its launches.  One JSON line per
+(shape, payload), medians over the rounds.
+
+    python tools/bench_inflate.py [--rounds 7] [--warmup 2] [--shapes many,large]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+import zlib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = {  # name: (connections = messages, inflated bytes a message)
+    "many": (16384, 4096),
+    "large": (1024, 256 * 1024),
+}
+LEVELS = {"text": 6, "stored": 0}
+DISTINCT = 8
+TAIL = b"\x00\x00\xff\xff"
+WORDS = ("the quick brown fox jumps over the lazy dog while websocket frames carry compressed json payloads "
+         "status ok error null true false id name value timestamp price volume bid ask größe naïve €").split()
+
+
+def text(nbytes: int, rng) -> bytes:
+    """nbytes of word soup with numbers in it: compresses about 3:1."""
+    parts = []
+    size = 0
+    while size < nbytes + 8:
+        w = WORDS[int(rng.integers(0, len(WORDS)))] if rng.random() < 0.8 else str(int(rng.integers(0, 10 ** 6)))
+        parts.append(w)
+        size += len(w.encode()) + 1
+    b = " ".join(parts).encode()
+    cut = nbytes
+    while cut and (b[cut] & 0xC0) == 0x80:
+        cut -= 1
+    return b[:cut] + b"." * (nbytes - cut)
+
+
+def deflate(data: bytes, level: int) -> bytes:
+    c = zlib.compressobj(level, zlib.DEFLATED, -15)
+    s = c.compress(data) + c.flush(zlib.Z_SYNC_FLUSH)
+    assert s.endswith(TAIL)
+    return s[:-4]
+
+
+def wire_frame(payload: bytes, key: bytes):
+    import numpy as np
+    L = len(payload)
+    hdr = bytes([0xC1]) + (bytes([0x80 | L]) if L <= 125 else bytes([0x80 | 126]) + L.to_bytes(2, "big") if L <= 0xFFFF
+                           else bytes([0x80 | 127]) + L.to_bytes(8, "big")) + key  # FIN | RSV1 | text, masked
+    body = np.frombuffer(payload, np.uint8) ^ np.resize(np.frombuffer(key, np.uint8), L)
+    return np.concatenate([np.frombuffer(hdr, np.uint8), body])
+
+
+def inflate_all(job):
+    """zlib over `count` messages cycling through `payloads`: (seconds, bytes out)."""
+    payloads, count = job
+    t0 = time.perf_counter()
+    total = 0
+    for i in range(count):
+        total += len(zlib.decompressobj(-15).decompress(payloads[i % len(payloads)] + TAIL))
+    return time.perf_counter() - t0, total
+
+
+def cpu_baselines(payloads, n: int, rounds: int):
+    """Medians of the wall time zlib takes for the n messages: one core, and 16 processes sharing them."""
+    import multiprocessing as mp
+    one = sorted(inflate_all((payloads, n))[0] for _ in range(rounds))[rounds // 2]
+    jobs = [(payloads, n // 16 + (1 if k < n % 16 else 0)) for k in range(16)]
+    with mp.get_context("spawn").Pool(16) as pool:  # fresh interpreters: no GPU state in them
+        pool.map(inflate_all, jobs)  # warm-up: the workers are up
+        walls = []
+        for _ in range(rounds):
+            t0 = time.perf_counter()
+            pool.map(inflate_all, jobs)
+            walls.append(time.perf_counter() - t0)
+    return one, sorted(walls)[rounds // 2]
+
+
+def median(xs):
+    return sorted(xs)[len(xs) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--shapes", default="many,large")
+    ap.add_argument("--kinds", default="text,stored")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the zlib baselines")
+    args = ap.parse_args()
+    import numpy as np
+
+    rng = np.random.default_rng(0x696E66)
+    cases = []
+    for shape in args.shapes.split(","):
+        n, size = SHAPES[shape]
+        texts = [text(size, rng) for _ in range(DISTINCT)]
+        for kind in args.kinds.split(","):
+            payloads = [deflate(t, LEVELS[kind]) for t in texts]
+            cpu = (None, None) if args.no_cpu else cpu_baselines(payloads, n, args.rounds)
+            cases.append((shape, kind, n, size, texts, payloads, cpu))
+
+    import torch
+
+    import gev_amd
+
+    dev = torch.device("cuda", 0)
+    eng = gev_amd.Engine(0)
+    for shape, kind, n, size, texts, payloads, (cpu_one, cpu_16) in cases:
+        frames = [wire_frame(p, bytes(rng.integers(1, 256, 4).astype("u1"))) for p in payloads]
+        lens = np.array([frames[i % DISTINCT].size for i in range(n)], np.int64)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]])
+        in_bytes = int(lens.sum())
+        host = np.concatenate([frames[i % DISTINCT] for i in range(n)])
+        arena = torch.zeros(in_bytes + gev_amd.IN_PAD, dtype=torch.uint8, device=dev)
+        arena[:in_bytes] = torch.from_numpy(host).to(dev)
+        del host
+        conns = torch.from_numpy(np.stack([offs, lens], 1)).to(dev)
+        comp_bytes = sum(len(payloads[i % DISTINCT]) for i in range(n))
+        payload_cap = sum((len(payloads[i % DISTINCT]) + 15) // 16 * 16 for i in range(n))
+        out = eng.alloc_batch(n, n, payload_cap)
+        msgs = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+        msg_of = torch.empty(n, dtype=torch.int64, device=dev)
+        conn_msg = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+        msum = torch.zeros(64, dtype=torch.uint8, device=dev)
+        ext = torch.ones(n, dtype=torch.uint8, device=dev)
+        inflated = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+        out_cap = n * ((size + 15) // 16 * 16)
+        d_out = torch.empty(out_cap, dtype=torch.uint8, device=dev)
+        isum = torch.zeros(64, dtype=torch.uint8, device=dev)
+
+        def decode():
+            eng.decode_async(arena, in_bytes, conns, n, out, n, payload_cap)
+
+        def messages():
+            eng.messages_ext_async(out.frames, n, out.conn_out, n, out.summary, out.payload, None, msgs, n, msg_of,
+                                   conn_msg, msum, ext)
+
+        def inflate():
+            eng.inflate_async(out.frames, n, msgs, n, msg_of, msum, out.payload, size, None, inflated, d_out, out_cap,
+                              isum)
+
+        for _ in range(args.warmup):
+            decode(), messages(), inflate()
+        torch.cuda.synchronize()
+        s = isum.cpu().numpy().view(gev_amd.SUMMARY_DTYPE)[0]
+        assert (int(s["status"]), int(s["frames"]), int(s["errors"]), int(s["payload_len"])) == (0, n, 0, n * size), s
+        rec = inflated.cpu().numpy().reshape(-1).view(gev_amd.INFLATED_DTYPE)
+        for i in (0, 1, DISTINCT - 1, n - 1):  # the bytes are the texts
+            o = int(rec["out_off"][i])
+            assert d_out[o:o + size].cpu().numpy().tobytes() == texts[i % DISTINCT], i
+        t_inf, t_msg, t_unmask, t_dec = [], [], [], []
+        eng.set_timing(True)
+        for _ in range(args.rounds):  # the three steps alternate
+            decode()
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            e[0].record()
+            messages()
+            e[1].record()
+            inflate()
+            e[2].record()
+            torch.cuda.synchronize()
+            ms, calls = eng.timing()
+            assert calls == 1
+            t_msg.append(e[0].elapsed_time(e[1]))
+            t_inf.append(e[1].elapsed_time(e[2]))
+            t_dec.append(sum(ms))
+            t_unmask.append(ms[3])
+        eng.set_timing(False)
+        m, u = median(t_inf), median(t_unmask)
+        line = {
+            "path": "inflate step (permessage-deflate, one wave per message) behind a decode and the message pass",
+            "shape": shape, "payload": kind, "zlib_level": LEVELS[kind], "messages": n, "message_bytes": size,
+            "compressed_bytes": comp_bytes, "inflated_bytes": n * size,
+            "inflate_ms": round(m, 4), "inflate_rounds_ms": [round(t, 4) for t in t_inf],
+            "inflate_out_GBps": round(n * size / m / 1e6, 2),
+            "messages_ms": round(median(t_msg), 4), "decode_ms": round(median(t_dec), 4),
+            "unmask_ms": round(u, 4), "unmask_rounds_ms": [round(t, 4) for t in t_unmask],
+            "unmask_read_plus_write_GBps": round(2 * comp_bytes / u / 1e6, 1),
+            "rounds": args.rounds, "warmup": args.warmup}
+        if cpu_one is not None:
+            line.update({"zlib_1core_ms": round(cpu_one * 1e3, 2),
+                         "zlib_1core_out_GBps": round(n * size / cpu_one / 1e9, 3),
+                         "zlib_16proc_ms": round(cpu_16 * 1e3, 2),
+                         "zlib_16proc_out_GBps": round(n * size / cpu_16 / 1e9, 3)})
+        print(json.dumps(line), flush=True)
+        del arena, out, msgs, msg_of, conn_msg, inflated, d_out
+        torch.cuda.empty_cache()
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
