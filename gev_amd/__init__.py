@@ -26,6 +26,7 @@ from . import _abi
 from ._abi import (MSG_BEGIN, MSG_END, MSG_ERR_CONTINUATION, MSG_ERR_CONTROL, MSG_ERR_INTERLEAVE, MSG_ERR_OPCODE,
                    MSG_ERR_RSV, MSG_ERR_UTF8, MSG_OK)
 from ._abi import EXT_DEFLATE, INF_DONE, INF_PENDING, MSG_COMPRESSED, MSG_ERR_DEFLATE, MSG_ERR_TOO_BIG
+from ._abi import DEFLATE_PLAIN_IF_NOT_SMALLER
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
                    SUMMARY_UNORDERED, TILE, Header)
@@ -53,7 +54,10 @@ CONN_MSG_DTYPE = np.dtype([("first_message", "<u8"), ("error_frame", "<u8"), ("n
                            ("error", "<i4"), ("reserved", "<u8")])
 INFLATED_DTYPE = np.dtype([("out_off", "<u8"), ("length", "<u8"), ("status", "u1"), ("flags", "u1"),
                            ("reserved", "u1", (14,))])
+DEFLATE_MSG_DTYPE = np.dtype([("payload_off", "<u8"), ("length", "<u8"), ("opcode", "u1"), ("window_bits", "u1"),
+                              ("reserved", "u1", (6,))])
 assert FRAME_DTYPE.itemsize == 32 and CONN_OUT_DTYPE.itemsize == 32 and INFLATED_DTYPE.itemsize == 32
+assert DEFLATE_MSG_DTYPE.itemsize == 24 and OUT_FRAME_DTYPE.itemsize == 32
 assert MSG_STATE_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 32 and CONN_MSG_DTYPE.itemsize == 32
 assert SUMMARY_DTYPE.itemsize == 64 and SYNTH_DTYPE.itemsize == 24
 
@@ -83,6 +87,25 @@ def inflate_raw(b: bytes, cap: int) -> Tuple[int, bytes]:
     if st < 0:
         raise RuntimeError(f"gevws_inflate_raw: {status_string(st)}")
     return st, out.raw[: n.value]
+
+
+def deflate_bound(n: int) -> int:
+    """gevws_deflate_bound: the most bytes a message of n plain bytes can become."""
+    return int(lib.gevws_deflate_bound(n))
+
+
+def deflate_raw(b: bytes, window_bits: int = 0) -> bytes:
+    """gevws_deflate_raw: one message compressed on the host by the compressor
+    the device runs -- the payload gevws_deflate_async writes for the same
+    bytes and window_bits (0 = 15, else 8..15), byte for byte."""
+    b = bytes(b)
+    cap = deflate_bound(len(b))
+    out = ctypes.create_string_buffer(cap)
+    n = ctypes.c_uint64(0)
+    st = lib.gevws_deflate_raw(ctypes.c_char_p(b), len(b), window_bits, out, cap, ctypes.byref(n))
+    if st != OK:
+        raise RuntimeError(f"gevws_deflate_raw: {status_string(st)}")
+    return out.raw[: n.value]
 
 
 def deflate_negotiate(value: bytes) -> bytes:
@@ -182,6 +205,28 @@ class Inflated:
         """The inflated bytes of message i (b"" when it has none)."""
         r = self.inflated_host()[i]
         off, n = int(r["out_off"]), int(r["length"])
+        return self.out[off: off + n].cpu().numpy().tobytes() if n else b""
+
+
+@dataclass
+class Deflated:
+    """Device-resident result of one deflate step (Engine.deflate)."""
+    frames: "object"      # uint8 [n_messages, 32]   (gevws_out_frame records, ready for encode_async)
+    out: "object"         # uint8 [out_cap + OUT_PAD] (the payloads, each on a 16-byte boundary)
+    summary: "object"     # uint8 [64]               (gevws_summary)
+    n_messages: int
+
+    def summary_host(self) -> np.ndarray:
+        return self.summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
+
+    def frames_host(self) -> np.ndarray:
+        n = int(self.summary_host()["frames"])
+        return self.frames[:n].cpu().numpy().reshape(-1).view(OUT_FRAME_DTYPE)
+
+    def payload(self, i: int) -> bytes:
+        """The wire payload of message i."""
+        r = self.frames_host()[i]
+        off, n = int(r["payload_off"]), int(r["payload_len"])
         return self.out[off: off + n].cpu().numpy().tobytes() if n else b""
 
 
@@ -547,6 +592,50 @@ class Engine:
                 raise RuntimeError(f"inflate: {status_string(int(s['status']))}")
             return res
         raise RuntimeError("inflate: capacity retry failed")
+
+    def deflate_async(self, msgs, max_msgs: int, prev, src, src_bytes: int, flags: int, out_frames, out,
+                      out_cap: int, summary, stream=None) -> None:
+        """gevws_deflate_async on device tensors: the messages of `msgs`
+        (DEFLATE_MSG_DTYPE rows as a uint8 [n, 24] tensor, their bytes in `src`)
+        compressed into `out` (>= out_cap + OUT_PAD bytes) with their
+        gevws_out_frame records in `out_frames`; prev: a producing step's
+        summary that gates the count, or None."""
+        st = lib.gevws_deflate_async(
+            self._ctx, _stream_handle(stream), msgs.data_ptr() if max_msgs else None, max_msgs,
+            prev.data_ptr() if prev is not None else None, src.data_ptr() if max_msgs else None, src_bytes, flags,
+            out_frames.data_ptr() if max_msgs else None, out.data_ptr() if max_msgs else None, out_cap,
+            summary.data_ptr())
+        if st != OK:
+            raise RuntimeError(f"gevws_deflate_async: {status_string(st)}")
+
+    def deflate(self, msgs: np.ndarray, src, src_bytes: int, flags: int = 0, out_cap: Optional[int] = None,
+                stream=None) -> "Deflated":
+        """The deflate step over host records (DEFLATE_MSG_DTYPE) whose bytes
+        live in the device tensor `src` (src_bytes + IN_PAD long).  Grows the
+        output once on ERR_CAPACITY (nothing is written by the call that did
+        not fit)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        n = int(msgs.shape[0])
+        d_msgs = torch.from_numpy(np.ascontiguousarray(msgs).view(np.uint8).reshape(-1, 24).copy()).to(dev) \
+            if n else torch.zeros((1, 24), dtype=torch.uint8, device=dev)
+        if out_cap is None:  # text compresses several-fold; the retry covers what does not
+            out_cap = int(msgs["length"].sum()) // 2 + 16 * n
+        for attempt in range(2):
+            res = Deflated(frames=torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=dev),
+                           out=torch.empty(out_cap + _abi.OUT_PAD, dtype=torch.uint8, device=dev),
+                           summary=torch.zeros(64, dtype=torch.uint8, device=dev), n_messages=n)
+            self.deflate_async(d_msgs, n, None, src, src_bytes, flags, res.frames, res.out, out_cap, res.summary,
+                               stream)
+            torch.cuda.synchronize(self.device)
+            s = res.summary_host()
+            if int(s["status"]) == ERR_CAPACITY and attempt == 0:
+                out_cap = int(s["payload_bytes"])
+                continue
+            if int(s["status"]) != OK:
+                raise RuntimeError(f"deflate: {status_string(int(s['status']))}")
+            return res
+        raise RuntimeError("deflate: capacity retry failed")
 
     def messages(self, out: "Batch", state=None, max_messages: Optional[int] = None, stream=None, *,
                  conn_ext=None) -> "Messages":
@@ -1185,4 +1274,5 @@ __all__ = ["Engine", "Batch", "Comm", "RingBuffer", "Connection", "Protocol", "H
            "Upgrader", "RejectError", "HandshakeError", "HandshakeInfo", "accept_key", "HANDSHAKE", "ERR_HANDSHAKE",
            "status_string", "device_count", "lib", "FRAME_DTYPE", "CONN_OUT_DTYPE", "SUMMARY_DTYPE",
            "SYNTH_DTYPE", "OUT_FRAME_DTYPE", "OK", "NEED_MORE", "ERR_LEN_MSB", "ERR_CAPACITY", "ERR_INVALID", "ERR_DEVICE",
-           "ERR_NOT_UPGRADED", "IN_PAD", "PAYLOAD_ALIGN", "TILE", "SUMMARY_UNORDERED"]
+           "ERR_NOT_UPGRADED", "IN_PAD", "PAYLOAD_ALIGN", "TILE", "SUMMARY_UNORDERED",
+           "DEFLATE_MSG_DTYPE", "DEFLATE_PLAIN_IF_NOT_SMALLER", "Deflated", "deflate_raw", "deflate_bound"]

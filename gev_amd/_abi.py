@@ -67,6 +67,7 @@ MSG_END = 2
 MSG_ERR_DEFLATE = 7
 MSG_ERR_TOO_BIG = 8
 MSG_COMPRESSED = 4
+DEFLATE_PLAIN_IF_NOT_SMALLER = 1  # gevws_deflate_async flag
 EXT_DEFLATE = 1
 INF_DONE = 1
 INF_PENDING = 2
@@ -153,6 +154,12 @@ class Message(ctypes.Structure):
 class ConnMsg(ctypes.Structure):
     _fields_ = [("first_message", ctypes.c_uint64), ("error_frame", ctypes.c_uint64),
                 ("nmessages", ctypes.c_uint32), ("error", ctypes.c_int32), ("reserved", ctypes.c_uint64)]
+
+
+class DeflateMsg(ctypes.Structure):
+    """gevws_deflate_msg: one outbound message for the deflate step."""
+    _fields_ = [("payload_off", ctypes.c_uint64), ("length", ctypes.c_uint64), ("opcode", ctypes.c_uint8),
+                ("window_bits", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 6)]
 
 
 class Inflated(ctypes.Structure):
@@ -261,6 +268,11 @@ SIGNATURES = {
     "gevws_inflate_raw": (ctypes.c_int, [P, ctypes.c_uint64, P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "gevws_deflate_negotiate": (ctypes.c_int, [P, ctypes.c_uint64, P, ctypes.c_uint64,
                                                ctypes.POINTER(ctypes.c_uint64)]),
+    "gevws_deflate_bound": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "gevws_deflate_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, ctypes.c_uint64, ctypes.c_uint32, P, P,
+                                           ctypes.c_uint64, P]),
+    "gevws_deflate_raw": (ctypes.c_int, [P, ctypes.c_uint64, ctypes.c_int, P, ctypes.c_uint64,
+                                         ctypes.POINTER(ctypes.c_uint64)]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),
     "gevws_synth_async": (ctypes.c_int, [P, P, P, P, ctypes.c_uint64, ctypes.c_uint64]),
     "gevws_synth_verify_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P,

@@ -1,0 +1,124 @@
+// gevws_deflate_host.cpp -- gevws_deflate_raw and gevws_deflate_bound
+// (include/gevws.h): the compressor of gevws_deflate_core.hpp on host memory,
+// the 64 positions of a step taken one after the other.  Plain C++: it also
+// builds outside the library, under sanitizers (tests/cpp/deflate_fuzz.cpp).
+#include <cstring>
+
+#include "gevws.h"
+#include "gevws_deflate_core.hpp"
+
+namespace {
+
+using namespace gevws_deflate;
+
+// A run's bits before they are final: a fixed block of kRun 9-bit literals,
+// the partial byte before it and the step's slack.
+constexpr uint32_t kOutBytes = kRun + kRun / 8 + 128;
+
+struct HostW {
+  struct Reader {
+    const uint8_t* in;
+    uint64_t n;
+    uint32_t u32(uint64_t pos) const {  // zeros past the message (the core clamps before they count)
+      uint32_t v = 0;
+      for (uint32_t i = 0; i < 4 && pos + i < n; ++i) v |= (uint32_t)in[pos + i] << (8 * i);
+      return v;
+    }
+    uint64_t u64(uint64_t pos) const { return (uint64_t)u32(pos) | ((uint64_t)u32(pos + 4) << 32); }
+  } rd;
+  uint8_t* out;          // NULL: sizing
+  uint64_t flushed = 0;  // bytes of out that are final; obuf[0] is byte `flushed`
+  uint64_t p0 = 0;
+  uint32_t cnt = 0;
+  uint16_t tab[kHashSlots];
+  uint32_t len[kLanes], dist[kLanes];
+  uint8_t obuf[kOutBytes];
+
+  HostW(const uint8_t* in, uint64_t n, uint8_t* out_) : rd{in, n}, out(out_) {
+    memset(tab, 0, sizeof(tab));
+    memset(obuf, 0, sizeof(obuf));
+  }
+  void stage(uint64_t, uint64_t) {}
+  void find(uint64_t p0_, uint32_t cnt_, uint64_t run_end, uint64_t n, uint32_t maxd) {
+    p0 = p0_, cnt = cnt_;
+    uint32_t h[kLanes];
+    for (uint32_t l = 0; l < cnt; ++l) {  // every lookup sees the table as the step found it
+      const uint64_t p = p0 + l;
+      len[l] = dist[l] = 0;
+      h[l] = kHashSlots;
+      if (p + 4 > n) continue;
+      h[l] = hash4(rd.u32(p));
+      match_one(rd, p, tab[h[l]], run_end, maxd, len[l], dist[l]);
+    }
+    for (uint32_t l = cnt; l-- > 0;)  // in falling order: the step's lowest position takes the slot ...
+      if (h[l] < kHashSlots) tab[h[l]] = (uint16_t)(p0 + l);
+    for (uint32_t l = 0; l < cnt; ++l)  // ... as every position's second candidate
+      if (h[l] < kHashSlots) second_one(rd, p0 + l, tab[h[l]], run_end, maxd, len[l], dist[l]);
+    for (uint32_t l = 0; l < cnt; ++l)  // in rising order: the highest position keeps the slot
+      if (h[l] < kHashSlots) tab[h[l]] = (uint16_t)(p0 + l);
+  }
+  uint64_t match_mask() const {
+    uint64_t m = 0;
+    for (uint32_t l = 0; l < cnt; ++l) m |= (uint64_t)(len[l] != 0) << l;
+    return m;
+  }
+  uint32_t len_at(uint32_t i) const { return len[i]; }
+  void or_bits(uint64_t bit, uint32_t v) {
+    const uint64_t o = bit - 8 * flushed;
+    uint64_t x = (uint64_t)v << (o & 7);
+    for (uint64_t i = o >> 3; x; ++i, x >>= 8) obuf[i] |= (uint8_t)x;
+  }
+  template <bool EMIT>
+  uint32_t tokens(uint64_t lits, uint64_t take, uint64_t bit) {
+    uint32_t total = 0;
+    for (uint32_t l = 0; l < cnt; ++l) {
+      uint32_t nb = 0, code = 0;
+      if ((lits >> l) & 1) code = lit_code(rd.in[p0 + l], nb);
+      else if ((take >> l) & 1) code = match_code(len[l], dist[l], nb);
+      if (EMIT && nb) or_bits(bit + total, code);
+      total += nb;
+    }
+    return total;
+  }
+  void begin_run(uint64_t) {}
+  void rewind(uint64_t bit0) {
+    const uint64_t o = bit0 - 8 * flushed;  // (< 8: end_run left a partial byte at most)
+    obuf[o >> 3] &= (uint8_t)((1u << (o & 7)) - 1);
+    memset(obuf + (o >> 3) + 1, 0, sizeof(obuf) - (o >> 3) - 1);
+  }
+  void put_bits(uint64_t bit, uint32_t v, uint32_t) { or_bits(bit, v); }
+  void stored(uint64_t src, uint32_t n, uint64_t byte) { memcpy(obuf + (byte - flushed), rd.in + src, n); }
+  void end_run(uint64_t bit) {
+    const uint64_t whole = (bit >> 3) - flushed;
+    memcpy(out + flushed, obuf, whole);
+    const uint8_t part = obuf[whole];
+    memset(obuf, 0, sizeof(obuf));
+    obuf[0] = part;
+    flushed += whole;
+  }
+  void finish(uint64_t bytes) {
+    if (bytes > flushed) memcpy(out + flushed, obuf, bytes - flushed);
+  }
+};
+
+}  // namespace
+
+extern "C" uint64_t gevws_deflate_bound(uint64_t n) { return gevws_deflate::bound(n); }
+
+extern "C" int gevws_deflate_raw(const uint8_t* in, uint64_t n, int window_bits, uint8_t* out, uint64_t cap,
+                                 uint64_t* out_len) {
+  if (out_len) *out_len = 0;
+  if ((n && !in) || (cap && !out) || n > 0xFFFFFFFFull || (window_bits != 0 && (window_bits < 8 || window_bits > 15)))
+    return GEVWS_ERR_INVALID;
+  const uint32_t maxd = max_dist((uint32_t)window_bits);
+  uint64_t need;
+  {
+    HostW w(in, n, nullptr);
+    need = deflate<false>(w, n, maxd);
+  }
+  if (out_len) *out_len = need;
+  if (need > cap) return GEVWS_ERR_CAPACITY;
+  HostW w(in, n, out);
+  const uint64_t got = deflate<true>(w, n, maxd);
+  return got == need ? GEVWS_OK : GEVWS_ERR_INVALID;  // (the two passes are one algorithm)
+}

@@ -601,14 +601,87 @@ int gevws_inflate_raw(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap,
  * that inflates on the device: the first permessage-deflate offer it can
  * serve is answered with
  *   permessage-deflate; client_no_context_takeover; server_no_context_takeover
- * plus "; server_max_window_bits=N" when the offer carried it (the server
- * never compresses, so any N in 8..15 holds).  client_max_window_bits, with
+ * plus "; server_max_window_bits=N" when the offer carried it (any N in 8..15:
+ * a server that compresses hands N to gevws_deflate_async as a message's
+ * window_bits, one that answers uncompressed holds any N).  client_max_window_bits, with
  * or without a value in 8..15, is accepted and not echoed.  An offer with an
  * unknown parameter, a repeated one or a bad value is skipped.  *out_len = the
  * answer's length, 0 when no offer is usable or the value is malformed.
  * Returns GEVWS_OK, or GEVWS_ERR_CAPACITY when the answer does not fit
  * out[0, cap).  Meant to be called from the upgrader's extension_custom hook. */
 int gevws_deflate_negotiate(const uint8_t *offer, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len);
+
+/* The deflate step: outbound messages compressed on the device, and the
+ * gevws_out_frame records gevws_encode_batch_async frames them from.
+ * Additions to ABI version 3: nothing above changes.
+ *
+ * Input.  d_msgs[i] is one message to send: its plain bytes are
+ * d_src[payload_off, payload_off + length).  d_src has GEVWS_IN_PAD readable
+ * bytes past src_bytes and is read as whole 16-byte vectors, but only `length`
+ * bytes count.  The messages are the first max_msgs records, or with d_prev
+ * the first min(d_prev->frames, max_msgs), none when d_prev->status < 0 (read
+ * on the device, as gevws_dispatch_decoded_async reads d_decoded).  No
+ * messages give a zero summary and read none of the inputs.
+ *
+ * Payload (RFC 7692 section 7.2.1).  A raw DEFLATE stream (RFC 1951) of
+ * blocks with BFINAL 0, closed by an empty stored block whose last four bytes
+ * 00 00 ff ff are taken off; an empty message is the single byte 00.  Blocks
+ * are fixed-Huffman (BTYPE 01) with LZ77 matches of length 3..258, or stored
+ * (BTYPE 00) wherever that is smaller; no dynamic codes.  No match distance
+ * exceeds 2^window_bits (0 stands for 15), so an answer that carried
+ * server_max_window_bits=N is honoured with window_bits = N.  Every message
+ * starts from an empty window: server_no_context_takeover, which
+ * gevws_deflate_negotiate puts into every answer.  The bytes are valid
+ * DEFLATE, not zlib's; they depend only on the message's bytes and its
+ * window_bits -- not on its place in the batch, its neighbours, the pad
+ * behind it or the grid -- and gevws_deflate_raw gives the same bytes.
+ *
+ * Output.  d_out_frames[i] = {hdr = {fin 1, rsv 4 (RSV1), opcode, masked 0,
+ * mask 0, length c}, payload_off, payload_len c} with c the compressed
+ * length; the payloads lie in d_out in message order, each on a
+ * GEVWS_PAYLOAD_ALIGN boundary, the pad behind each zeroed.  d_out needs
+ * GEVWS_OUT_PAD writable bytes past out_cap; it is then gevws_encode_batch_async's
+ * d_payload as it stands.  With GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER in `flags`
+ * a message with c >= length goes out plain: rsv 0, its bytes verbatim (RFC
+ * 7692 section 6 leaves the choice to the sender, message by message).
+ *
+ * d_summary: frames = records written, payload_bytes = bytes of d_out used,
+ * payload_len = the sum of the wire payload lengths, errors 0.  status
+ * GEVWS_ERR_CAPACITY when out_cap is too small: payload_bytes then holds the
+ * need and nothing else is written, so the caller retries.  status
+ * GEVWS_ERR_INVALID when a record is malformed -- an opcode other than 1 / 2,
+ * window_bits outside {0, 8..15}, payload_off not on GEVWS_PAYLOAD_ALIGN, a
+ * range outside d_src[0, src_bytes), a length above 2^32 - 1: errors then
+ * counts such records, the other fields are zero and nothing else is written. */
+#define GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER 1u     /* call flag */
+typedef struct gevws_deflate_msg {   /* 24 bytes: one message to send */
+    uint64_t payload_off;   /* into d_src, a multiple of GEVWS_PAYLOAD_ALIGN */
+    uint64_t length;        /* plain bytes, <= 2^32 - 1 */
+    uint8_t opcode;         /* 1 text, 2 binary */
+    uint8_t window_bits;    /* 0 = 15; else 8..15: the negotiated server_max_window_bits */
+    uint8_t reserved[6];    /* zero */
+} gevws_deflate_msg;
+
+/* The most bytes a message of n plain bytes can become:
+ * n + 5 * ceil(n / 4096) + 1 <= n + n / 512 + 16 (a stored block costs at
+ * most 5 bytes, and the compressor decides per 4 KiB of input). */
+uint64_t gevws_deflate_bound(uint64_t n);
+
+int gevws_deflate_async(gevws_ctx *ctx, void *stream,
+                        const gevws_deflate_msg *d_msgs, uint64_t max_msgs,
+                        const gevws_summary *d_prev /* may be NULL */,
+                        const uint8_t *d_src, uint64_t src_bytes, uint32_t flags,
+                        gevws_out_frame *d_out_frames, uint8_t *d_out, uint64_t out_cap,
+                        gevws_summary *d_summary);
+
+/* The same compressor on host memory: in[0, n) is one message, window_bits as
+ * in gevws_deflate_msg, out[0, cap) receives the payload the device would
+ * write for it, byte for byte.  Returns GEVWS_OK; GEVWS_ERR_CAPACITY when the
+ * payload does not fit (*out_len = the need, out untouched); GEVWS_ERR_INVALID
+ * for a NULL buffer, n above 2^32 - 1 or a window_bits outside {0, 8..15}.
+ * *out_len = the payload's length. */
+int gevws_deflate_raw(const uint8_t *in, uint64_t n, int window_bits,
+                      uint8_t *out, uint64_t cap, uint64_t *out_len);
 
 /* Measurement helper, not on the reference path: n bytes (n % 16 == 0, d_dst
  * 16-byte aligned, d_src any alignment) copied with the unmask kernel's

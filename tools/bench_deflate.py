@@ -1,0 +1,194 @@
+#!/usr/bin/env python3
+"""Measure the deflate step (gevws_deflate_async: one wave per outbound
+message, fixed-Huffman and stored blocks) beside baselines for the same batch:
+zlib level 1 with Z_FIXED (the same block types) and zlib level 1 with its
+default strategy (dynamic codes), each on one core and on 16 processes of this
+machine, and the unmask of a decode of a batch of the same sizes
+(gevws_ctx_timing), which is what moving the bytes once costs.
+
+Two shapes -- 16 384 messages of 4 KiB and 1 024 of 256 KiB -- times two
+payloads: the word soup of tools/bench_inflate.py and random bytes (stored
+blocks: the copy bound of this step).  A shape's messages cycle through eight
+distinct payloads.  The decode and the deflate step alternate in one process;
+the deflate step is timed by HIP events around its launches.  One JSON line
+per (shape, payload), medians over the rounds.
+
+    python tools/bench_deflate.py [--rounds 7] [--warmup 2] [--shapes many,large] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+import zlib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from bench_inflate import DISTINCT, SHAPES, TAIL, median, text  # noqa: E402
+
+ZLIB = {"zlib1_fixed": zlib.Z_FIXED, "zlib1_default": zlib.Z_DEFAULT_STRATEGY}
+
+
+def zdeflate(data: bytes, strategy: int) -> bytes:
+    c = zlib.compressobj(1, zlib.DEFLATED, -15, 8, strategy)
+    return (c.compress(data) + c.flush(zlib.Z_SYNC_FLUSH))[:-4]
+
+
+def deflate_all(job):
+    """zlib level 1 over `count` messages cycling through `plains`: (seconds, bytes out)."""
+    plains, count, strategy = job
+    t0 = time.perf_counter()
+    total = 0
+    for i in range(count):
+        total += len(zdeflate(plains[i % len(plains)], strategy))
+    return time.perf_counter() - t0, total
+
+
+def cpu_baselines(plains, n: int, rounds: int, strategy: int):
+    """Medians of the wall time zlib takes for the n messages: one core, and 16 processes sharing them."""
+    import multiprocessing as mp
+    one = median([deflate_all((plains, n, strategy))[0] for _ in range(rounds)])
+    jobs = [(plains, n // 16 + (1 if k < n % 16 else 0), strategy) for k in range(16)]
+    with mp.get_context("spawn").Pool(16) as pool:  # fresh interpreters: no GPU state in them
+        pool.map(deflate_all, jobs)  # warm-up: the workers are up
+        walls = []
+        for _ in range(rounds):
+            t0 = time.perf_counter()
+            pool.map(deflate_all, jobs)
+            walls.append(time.perf_counter() - t0)
+    return one, median(walls)
+
+
+def masked_frame(payload: bytes, key: bytes):
+    import numpy as np
+    L = len(payload)
+    hdr = bytes([0x82]) + (bytes([0x80 | L]) if L <= 125 else bytes([0x80 | 126]) + L.to_bytes(2, "big") if L <= 0xFFFF
+                           else bytes([0x80 | 127]) + L.to_bytes(8, "big")) + key  # FIN | binary, masked
+    body = np.frombuffer(payload, np.uint8) ^ np.resize(np.frombuffer(key, np.uint8), L)
+    return np.concatenate([np.frombuffer(hdr, np.uint8), body])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--shapes", default="many,large")
+    ap.add_argument("--kinds", default="text,random")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the zlib baselines")
+    ap.add_argument("--out", default=None, help="append the lines to this file too")
+    args = ap.parse_args()
+    import numpy as np
+
+    rng = np.random.default_rng(0x646566)
+    cases = []
+    for shape in args.shapes.split(","):
+        n, size = SHAPES[shape]
+        for kind in args.kinds.split(","):
+            plains = [text(size, rng) if kind == "text" else rng.integers(0, 256, size, dtype=np.uint8).tobytes()
+                      for _ in range(DISTINCT)]
+            cpu = {}
+            for name, strategy in ZLIB.items():
+                cpu[name] = {"bytes": sum(len(zdeflate(plains[i % DISTINCT], strategy)) for i in range(DISTINCT))
+                             * (n // DISTINCT)}
+                if not args.no_cpu:
+                    cpu[name]["one"], cpu[name]["p16"] = cpu_baselines(plains, n, args.rounds, strategy)
+                    print(f"[bench_deflate] {shape} {kind} {name}: 1 core {cpu[name]['one'] * 1e3:.0f} ms, "
+                          f"16 processes {cpu[name]['p16'] * 1e3:.0f} ms", file=sys.stderr, flush=True)
+            cases.append((shape, kind, n, size, plains, cpu))
+
+    import torch
+
+    import gev_amd
+
+    dev = torch.device("cuda", 0)
+    eng = gev_amd.Engine(0)
+    for shape, kind, n, size, plains, cpu in cases:
+        assert size % 16 == 0 and n % DISTINCT == 0
+        # the step's input: the messages back to back, each on a 16-byte boundary
+        src_bytes = n * size
+        src = torch.empty(src_bytes + gev_amd.IN_PAD, dtype=torch.uint8, device=dev)
+        block = torch.from_numpy(np.frombuffer(b"".join(plains), np.uint8).copy()).to(dev)
+        src[:src_bytes].view(n // DISTINCT, DISTINCT * size)[:] = block
+        rec = np.zeros(n, gev_amd.DEFLATE_MSG_DTYPE)
+        rec["payload_off"], rec["length"], rec["opcode"] = np.arange(n, dtype=np.uint64) * size, size, 2
+        d_rec = torch.from_numpy(rec.view(np.uint8).reshape(-1, 24).copy()).to(dev)
+        out_cap = n * ((gev_amd.deflate_bound(size) + 15) // 16 * 16)
+        d_out = torch.empty(out_cap + gev_amd._abi.OUT_PAD, dtype=torch.uint8, device=dev)
+        d_frames = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+        dsum = torch.zeros(64, dtype=torch.uint8, device=dev)
+        # a decode of masked frames of the same sizes: its unmask is the yardstick for moving the bytes
+        frames = [masked_frame(p, bytes(rng.integers(1, 256, 4).astype("u1"))) for p in plains]
+        lens = np.array([frames[i % DISTINCT].size for i in range(n)], np.int64)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]])
+        in_bytes = int(lens.sum())
+        arena = torch.zeros(in_bytes + gev_amd.IN_PAD, dtype=torch.uint8, device=dev)
+        arena[:in_bytes] = torch.from_numpy(np.concatenate([frames[i % DISTINCT] for i in range(n)])).to(dev)
+        conns = torch.from_numpy(np.stack([offs, lens], 1)).to(dev)
+        out = eng.alloc_batch(n, n, n * size)
+
+        def decode():
+            eng.decode_async(arena, in_bytes, conns, n, out, n, n * size)
+
+        def deflate():
+            eng.deflate_async(d_rec, n, None, src, src_bytes, 0, d_frames, d_out, out_cap, dsum)
+
+        for _ in range(args.warmup):
+            decode(), deflate()
+        torch.cuda.synchronize()
+        s = dsum.cpu().numpy().view(gev_amd.SUMMARY_DTYPE)[0]
+        assert (int(s["status"]), int(s["frames"]), int(s["errors"])) == (0, n, 0), s
+        comp_bytes = int(s["payload_len"])
+        fr = d_frames.cpu().numpy().reshape(-1).view(gev_amd.OUT_FRAME_DTYPE)
+        for i in (0, 1, DISTINCT - 1, n - 1):  # the payloads inflate to the messages
+            o, c = int(fr["payload_off"][i]), int(fr["payload_len"][i])
+            p = d_out[o:o + c].cpu().numpy().tobytes()
+            assert zlib.decompressobj(-15).decompress(p + TAIL) == plains[i % DISTINCT], i
+        t_def, t_unmask = [], []
+        eng.set_timing(True)
+        for _ in range(args.rounds):  # the two alternate
+            decode()
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            e[0].record()
+            deflate()
+            e[1].record()
+            torch.cuda.synchronize()
+            ms, calls = eng.timing()
+            assert calls == 1
+            t_def.append(e[0].elapsed_time(e[1]))
+            t_unmask.append(ms[3])
+        eng.set_timing(False)
+        m, u = median(t_def), median(t_unmask)
+        line = {
+            "path": "deflate step (permessage-deflate outbound, one wave per message, compressed twice: size, emit)",
+            "shape": shape, "payload": kind, "messages": n, "message_bytes": size, "plain_bytes": n * size,
+            "compressed_bytes": comp_bytes, "ratio": round(comp_bytes / (n * size), 4),
+            "deflate_ms": round(m, 4), "deflate_rounds_ms": [round(t, 4) for t in t_def],
+            "deflate_in_GBps": round(n * size / m / 1e6, 2), "deflate_out_GBps": round(comp_bytes / m / 1e6, 2),
+            "unmask_ms": round(u, 4), "unmask_rounds_ms": [round(t, 4) for t in t_unmask],
+            "unmask_read_plus_write_GBps": round(2 * n * size / u / 1e6, 1),
+            "rounds": args.rounds, "warmup": args.warmup}
+        for name, c in cpu.items():
+            line[f"{name}_bytes"] = c["bytes"]
+            line[f"size_vs_{name}"] = round(comp_bytes / c["bytes"], 4)
+            if "one" in c:
+                line.update({f"{name}_1core_ms": round(c["one"] * 1e3, 2),
+                             f"{name}_1core_in_GBps": round(n * size / c["one"] / 1e9, 3),
+                             f"{name}_16proc_ms": round(c["p16"] * 1e3, 2),
+                             f"{name}_16proc_in_GBps": round(n * size / c["p16"] / 1e9, 3)})
+        text_line = json.dumps(line)
+        print(text_line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as f:
+                f.write(text_line + "\n")
+        del src, d_out, d_frames, arena, out
+        torch.cuda.empty_cache()
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
