@@ -26,7 +26,7 @@ from . import _abi
 from ._abi import (MSG_BEGIN, MSG_END, MSG_ERR_CONTINUATION, MSG_ERR_CONTROL, MSG_ERR_INTERLEAVE, MSG_ERR_OPCODE,
                    MSG_ERR_RSV, MSG_ERR_UTF8, MSG_OK)
 from ._abi import EXT_DEFLATE, INF_DONE, INF_PENDING, MSG_COMPRESSED, MSG_ERR_DEFLATE, MSG_ERR_TOO_BIG
-from ._abi import DEFLATE_PLAIN_IF_NOT_SMALLER
+from ._abi import DEFLATE_DYNAMIC, DEFLATE_PLAIN_IF_NOT_SMALLER
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
                    SUMMARY_UNORDERED, TILE, Header)
@@ -94,17 +94,18 @@ def deflate_bound(n: int) -> int:
     return int(lib.gevws_deflate_bound(n))
 
 
-def deflate_raw(b: bytes, window_bits: int = 0) -> bytes:
-    """gevws_deflate_raw: one message compressed on the host by the compressor
-    the device runs -- the payload gevws_deflate_async writes for the same
-    bytes and window_bits (0 = 15, else 8..15), byte for byte."""
+def deflate_raw(b: bytes, window_bits: int = 0, flags: int = 0) -> bytes:
+    """gevws_deflate_raw_flags: one message compressed on the host by the
+    compressor the device runs -- the payload gevws_deflate_async writes for
+    the same bytes, window_bits (0 = 15, else 8..15) and flags (0 or
+    DEFLATE_DYNAMIC), byte for byte."""
     b = bytes(b)
     cap = deflate_bound(len(b))
     out = ctypes.create_string_buffer(cap)
     n = ctypes.c_uint64(0)
-    st = lib.gevws_deflate_raw(ctypes.c_char_p(b), len(b), window_bits, out, cap, ctypes.byref(n))
+    st = lib.gevws_deflate_raw_flags(ctypes.c_char_p(b), len(b), window_bits, flags, out, cap, ctypes.byref(n))
     if st != OK:
-        raise RuntimeError(f"gevws_deflate_raw: {status_string(st)}")
+        raise RuntimeError(f"gevws_deflate_raw_flags: {status_string(st)}")
     return out.raw[: n.value]
 
 
@@ -1275,4 +1276,4 @@ __all__ = ["Engine", "Batch", "Comm", "RingBuffer", "Connection", "Protocol", "H
            "status_string", "device_count", "lib", "FRAME_DTYPE", "CONN_OUT_DTYPE", "SUMMARY_DTYPE",
            "SYNTH_DTYPE", "OUT_FRAME_DTYPE", "OK", "NEED_MORE", "ERR_LEN_MSB", "ERR_CAPACITY", "ERR_INVALID", "ERR_DEVICE",
            "ERR_NOT_UPGRADED", "IN_PAD", "PAYLOAD_ALIGN", "TILE", "SUMMARY_UNORDERED",
-           "DEFLATE_MSG_DTYPE", "DEFLATE_PLAIN_IF_NOT_SMALLER", "Deflated", "deflate_raw", "deflate_bound"]
+           "DEFLATE_MSG_DTYPE", "DEFLATE_PLAIN_IF_NOT_SMALLER", "DEFLATE_DYNAMIC", "Deflated", "deflate_raw", "deflate_bound"]

@@ -68,6 +68,7 @@ MSG_ERR_DEFLATE = 7
 MSG_ERR_TOO_BIG = 8
 MSG_COMPRESSED = 4
 DEFLATE_PLAIN_IF_NOT_SMALLER = 1  # gevws_deflate_async flag
+DEFLATE_DYNAMIC = 2  # gevws_deflate_async / gevws_deflate_raw_flags flag
 EXT_DEFLATE = 1
 INF_DONE = 1
 INF_PENDING = 2
@@ -273,6 +274,8 @@ SIGNATURES = {
                                            ctypes.c_uint64, P]),
     "gevws_deflate_raw": (ctypes.c_int, [P, ctypes.c_uint64, ctypes.c_int, P, ctypes.c_uint64,
                                          ctypes.POINTER(ctypes.c_uint64)]),
+    "gevws_deflate_raw_flags": (ctypes.c_int, [P, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, P, ctypes.c_uint64,
+                                               ctypes.POINTER(ctypes.c_uint64)]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),
     "gevws_synth_async": (ctypes.c_int, [P, P, P, P, ctypes.c_uint64, ctypes.c_uint64]),
     "gevws_synth_verify_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P,

@@ -25,6 +25,10 @@
 // sizing, + the 4 736-byte staging buffer = 44.6 KiB when emitting: 4 and 3
 // waves a CU of its 160 KiB.  A wave's LDS accesses complete in order, so the
 // lanes hand bytes to each other through LDS without a barrier.
+//
+// With GEVWS_DEFLATE_DYNAMIC the two kernels run as k_def_size<true> /
+// k_def_emit<true>: a run may become a dynamic-Huffman block (DefWaveDyn
+// below).  46 032 B of LDS when sizing, 53 496 B when emitting: 3 waves a CU.
 #include "gevws_deflate_core.hpp"
 #include "gevws_internal.hpp"
 
@@ -234,7 +238,148 @@ struct DefWave {
   }
 };
 
+// GEVWS_DEFLATE_DYNAMIC: the histogram and the code table T in LDS, and when
+// emitting the run's tokens until its code is known -- a literal mask and a
+// match mask over the run's positions and the matches in order (literals are
+// read again from the window).  The construction's scratch is the staging
+// buffer's tail when emitting (nothing of the run is written before the code is
+// known, and the header ends below it), an array of its own when sizing.
+constexpr uint32_t kMaskWords = kRun / 64 + 1;
+constexpr uint32_t kScrAt = kOutWords - kScrWords;  // (when emitting)
+static_assert(kScrWords <= kOutWords && kScrAt % 4 == 0 && kScrAt * 32 >= 128 + 3 + kMaxHeaderBits + 64,
+              "the dynamic header ends below the scratch in the staging buffer");
+
+template <bool EMIT>
+struct DefWaveDyn : DefWave<EMIT> {
+  using B = DefWave<EMIT>;
+  uint32_t* T;       // kTab
+  uint32_t* scr;     // kScrWords
+  uint64_t* lm;      // EMIT: kMaskWords, the literal positions of the run
+  uint64_t* tm;      // EMIT: kMaskWords, the positions where a match starts
+  uint32_t* match;   // EMIT: kMaxMatches, (len - 3) | dist << 8 in order
+  uint32_t nmatch = 0;
+
+  __device__ DefWaveDyn(uint32_t* ring_, uint16_t* tab_, uint32_t* obuf_, const uint8_t* src_, uint8_t* out_,
+                        uint64_t slot_, uint32_t* T_, uint32_t* scr_, uint64_t* lm_, uint64_t* tm_, uint32_t* match_)
+      : B(ring_, tab_, obuf_, src_, out_, slot_), T(T_), scr(scr_), lm(lm_), tm(tm_), match(match_) {}
+
+  __device__ __forceinline__ uint32_t* table() { return T; }
+  __device__ __forceinline__ uint32_t* scratch() { return scr; }
+  __device__ __forceinline__ void sync() { wave_lds_order(); }
+  template <class F>
+  __device__ __forceinline__ uint32_t sum_n(uint32_t cnt, F f) {
+    uint32_t a = 0;
+    for (uint32_t i = B::lane; i < cnt; i += kDefBlock) a += f(i);
+    wave_lds_order();
+    return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan32_dpp(a), 63);
+  }
+  // Every lane holds the keys (count, index) of up to five symbols and counts
+  // the smaller keys as they come by, lane after lane: no sorting network, no
+  // LDS traffic but the stores of the result.
+  __device__ __forceinline__ uint32_t rank(const uint32_t* T_, uint32_t N, uint32_t* A, uint32_t* S) {
+    constexpr uint32_t K = kTab / kDefBlock;
+    uint32_t key[K], r[K];
+#pragma unroll
+    for (uint32_t k = 0; k < K; ++k) {
+      const uint32_t s = kDefBlock * k + B::lane, c = s < N ? tab_cnt(T_[s]) : 0u;
+      key[k] = c ? (c << 16) | s : ~0u;
+      r[k] = 0;
+    }
+    uint32_t n = 0;
+#pragma unroll
+    for (uint32_t kk = 0; kk < K; ++kk) {
+      if (kDefBlock * kk >= N) break;
+      n += (uint32_t)__popcll(__ballot(key[kk] != ~0u));
+      for (uint32_t j = 0; j < kDefBlock; ++j) {
+        const uint32_t kt = (uint32_t)__builtin_amdgcn_readlane((int)key[kk], (int)j);
+#pragma unroll
+        for (uint32_t k = 0; k < K; ++k) r[k] += kt < key[k] ? 1u : 0u;
+      }
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < K; ++k)
+      if (key[k] != ~0u) A[r[k]] = key[k] >> 16, S[r[k]] = key[k] & 0xffffu;  // (r < the used symbols <= N)
+    wave_lds_order();
+    return n;
+  }
+  template <bool E, class F>
+  __device__ __forceinline__ uint32_t emit_n(uint32_t cnt, uint64_t bit, F f) {
+    uint32_t total = 0;
+    for (uint32_t i0 = 0; i0 < cnt; i0 += kDefBlock) {
+      uint32_t nb = 0, code = 0;
+      if (i0 + B::lane < cnt) code = f(i0 + B::lane, nb);
+      const uint32_t incl = wave_incl_scan32_dpp(nb);
+      if (E && nb) B::or_bits(bit + total + (incl - nb), code);
+      total += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+    wave_lds_order();
+    return total;
+  }
+  __device__ __forceinline__ void begin_dyn() {
+    for (uint32_t j = B::lane; j < kTab; j += kDefBlock) T[j] = 0;
+    if (EMIT)
+      for (uint32_t j = B::lane; j < kMaskWords; j += kDefBlock) lm[j] = 0, tm[j] = 0;
+    nmatch = 0;
+    wave_lds_order();
+  }
+  template <bool E>
+  __device__ __forceinline__ void note(uint64_t lits, uint64_t take, uint32_t q) {
+    const uint32_t lane = B::lane;
+    if ((lits >> lane) & 1) {
+      __hip_atomic_fetch_add(T + B::byte, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    } else if ((take >> lane) & 1) {
+      uint32_t eb, ev;
+      __hip_atomic_fetch_add(T + 257 + len_sym(B::len, eb, ev), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(T + kLL + dist_sym(B::dist, eb, ev), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (E) {
+        const uint32_t k = nmatch + (uint32_t)__popcll(take & ((1ull << lane) - 1));
+        if (k < kMaxMatches) match[k] = (B::len - 3) | (B::dist << 8);  // (always: a match covers three positions)
+      }
+    }
+    if (E) {
+      const uint32_t w = q >> 6, sh = q & 63;  // (q < kRun: w + 1 < kMaskWords)
+      if (lane == 0) {
+        lm[w] |= lits << sh, tm[w] |= take << sh;
+        if (sh) lm[w + 1] |= lits >> (64 - sh), tm[w + 1] |= take >> (64 - sh);
+      }
+      nmatch += (uint32_t)__popcll(take);
+    }
+    wave_lds_order();
+  }
+  // The scratch lies in the staging buffer: zero again before the run's bits reach it.
+  __device__ __forceinline__ void scratch_done() {
+    if (!EMIT) return;
+    for (uint32_t j = B::lane; 4 * j < kScrWords; j += kDefBlock)
+      *reinterpret_cast<u32x4*>(scr + 4 * j) = u32x4{0, 0, 0, 0};
+    wave_lds_order();
+  }
+  __device__ __forceinline__ uint32_t replay(uint64_t rs, uint32_t rl, uint64_t bit) {
+    const uint32_t lane = B::lane;
+    uint32_t total = 0, k0 = 0;
+    for (uint32_t c = 0; 64 * c < rl; ++c) {
+      const uint64_t L = lm[c], M = tm[c];
+      uint32_t c1 = 0, n1 = 0, c2 = 0, n2 = 0;
+      if ((L >> lane) & 1) {
+        c1 = dyn_lit(T, B::rd.u32(rs + 64 * c + lane) & 0xffu, n1);
+      } else if ((M >> lane) & 1) {
+        const uint32_t k = k0 + (uint32_t)__popcll(M & ((1ull << lane) - 1));
+        const uint32_t m = k < kMaxMatches ? match[k] : 0u;
+        dyn_match(T, (m & 0xffu) + 3, (m >> 8) | (m >> 8 == 0), c1, n1, c2, n2);
+      }
+      const uint32_t incl = wave_incl_scan32_dpp(n1 + n2);
+      const uint64_t at = bit + total + (incl - n1 - n2);
+      if (n1) B::or_bits(at, c1);
+      if (n2) B::or_bits(at + n1, c2);
+      total += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      k0 += (uint32_t)__popcll(M);
+    }
+    wave_lds_order();
+    return total;
+  }
+};
+
 // ------------------------------------------------------------------ 1. checks and sizes
+template <bool DYN>
 __global__ __launch_bounds__(kDefBlock) void k_def_size(const gevws_deflate_msg* __restrict__ msgs, uint64_t max_msgs,
                                                         const gevws_summary* __restrict__ gate,
                                                         const uint8_t* __restrict__ src, uint64_t src_bytes,
@@ -256,8 +401,16 @@ __global__ __launch_bounds__(kDefBlock) void k_def_size(const gevws_deflate_msg*
   for (uint32_t j = threadIdx.x; j < kHashSlots / 8; j += kDefBlock)
     reinterpret_cast<u32x4*>(s_tab)[j] = u32x4{0, 0, 0, 0};
   wave_lds_order();
-  DefWave<false> w(s_ring, s_tab, nullptr, src + off, nullptr, 0);
-  const uint64_t c = deflate<false>(w, n, max_dist(wb));
+  uint64_t c;
+  if constexpr (DYN) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_T[kTab];
+    __shared__ __attribute__((aligned(16))) uint32_t s_scr[kScrWords];
+    DefWaveDyn<false> w(s_ring, s_tab, nullptr, src + off, nullptr, 0, s_T, s_scr, nullptr, nullptr, nullptr);
+    c = deflate_dyn<false>(w, n, max_dist(wb));
+  } else {
+    DefWave<false> w(s_ring, s_tab, nullptr, src + off, nullptr, 0);
+    c = deflate<false>(w, n, max_dist(wb));
+  }
   const bool plain = (flags & GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER) && c >= n;
   const uint64_t wire = plain ? n : c;
   if (threadIdx.x == 0) {
@@ -280,6 +433,7 @@ __global__ void k_def_verdict(gevws_summary* __restrict__ sum) {
 }
 
 // ------------------------------------------------------------------ 3. the bytes and the records
+template <bool DYN>
 __global__ __launch_bounds__(kDefBlock) void k_def_emit(const gevws_deflate_msg* __restrict__ msgs, uint64_t max_msgs,
                                                         const gevws_summary* __restrict__ gate,
                                                         const uint8_t* __restrict__ src,
@@ -326,8 +480,17 @@ __global__ __launch_bounds__(kDefBlock) void k_def_emit(const gevws_deflate_msg*
     reinterpret_cast<u32x4*>(s_out)[j] = u32x4{0, 0, 0, 0};
   wave_lds_order();
   // the sized length bounds the slot: the wave never writes past its allotted bytes
-  DefWave<true> w(s_ring, s_tab, s_out, p, q, round16(wire));
-  (void)deflate<true>(w, n, max_dist(uniform32(msg.window_bits)));
+  if constexpr (DYN) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_T[kTab];
+    __shared__ __attribute__((aligned(16))) uint64_t s_lm[kMaskWords];
+    __shared__ __attribute__((aligned(16))) uint64_t s_tm[kMaskWords];
+    __shared__ __attribute__((aligned(16))) uint32_t s_match[kMaxMatches];
+    DefWaveDyn<true> w(s_ring, s_tab, s_out, p, q, round16(wire), s_T, s_out + kScrAt, s_lm, s_tm, s_match);
+    (void)deflate_dyn<true>(w, n, max_dist(uniform32(msg.window_bits)));
+  } else {
+    DefWave<true> w(s_ring, s_tab, s_out, p, q, round16(wire));
+    (void)deflate<true>(w, n, max_dist(uniform32(msg.window_bits)));
+  }
 }
 
 }  // namespace
@@ -338,7 +501,8 @@ extern "C" int gevws_deflate_async(gevws_ctx* ctx, void* stream, const gevws_def
                                    const gevws_summary* d_prev, const uint8_t* d_src, uint64_t src_bytes,
                                    uint32_t flags, gevws_out_frame* d_out_frames, uint8_t* d_out, uint64_t out_cap,
                                    gevws_summary* d_summary) {
-  if (!ctx || !d_summary || max_msgs > 0x7FFFFFFFull || (flags & ~GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER))
+  if (!ctx || !d_summary || max_msgs > 0x7FFFFFFFull ||
+      (flags & ~(GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER | GEVWS_DEFLATE_DYNAMIC)))
     return GEVWS_ERR_INVALID;
   DeviceGuard g(ctx->device);
   hipStream_t st = pick_stream(ctx, stream);
@@ -354,10 +518,17 @@ extern "C" int gevws_deflate_async(gevws_ctx* ctx, void* stream, const gevws_def
   const DefScratch s = def_scratch(ctx->scratch, max_msgs);
   GEVWS_HIP(hipMemsetAsync(ctx->scratch, 0, s.total, st));
   const uint32_t nm = (uint32_t)max_msgs;
-  k_def_size<<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, src_bytes, flags, s.blk, s.rec);
+  const bool dyn = flags & GEVWS_DEFLATE_DYNAMIC;
+  if (dyn) k_def_size<true><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, src_bytes, flags, s.blk, s.rec);
+  else k_def_size<false><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, src_bytes, flags, s.blk, s.rec);
   k_scan_blocks<false><<<1, kScanBlock, 0, st>>>(s.blk, nm, UINT64_MAX, out_cap, d_summary);
   k_def_verdict<<<1, 1, 0, st>>>(d_summary);
-  k_def_emit<<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, s.blk, s.rec, d_summary, d_out_frames, d_out);
+  if (dyn)
+    k_def_emit<true><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, s.blk, s.rec, d_summary, d_out_frames,
+                                               d_out);
+  else
+    k_def_emit<false><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, s.blk, s.rec, d_summary, d_out_frames,
+                                                d_out);
   GEVWS_HIP(hipGetLastError());
   return mark_last(ctx, st);
 }

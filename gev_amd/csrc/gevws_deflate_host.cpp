@@ -1,4 +1,4 @@
-// gevws_deflate_host.cpp -- gevws_deflate_raw and gevws_deflate_bound
+// gevws_deflate_host.cpp -- gevws_deflate_raw, gevws_deflate_raw_flags and gevws_deflate_bound
 // (include/gevws.h): the compressor of gevws_deflate_core.hpp on host memory,
 // the 64 positions of a step taken one after the other.  Plain C++: it also
 // builds outside the library, under sanitizers (tests/cpp/deflate_fuzz.cpp).
@@ -101,24 +101,109 @@ struct HostW {
   }
 };
 
+// GEVWS_DEFLATE_DYNAMIC: the run's tokens are kept as the device keeps them --
+// a literal mask, a match mask and the matches in order -- and replayed once
+// the run's code is known.
+struct HostDynW : HostW, SerialSteps {
+  uint32_t tab32[kTab];
+  uint32_t scr[kScrWords];
+  uint64_t lm[kRun / 64 + 1], tm[kRun / 64 + 1];
+  uint32_t match[kMaxMatches];
+  uint32_t nmatch = 0;
+
+  HostDynW(const uint8_t* in, uint64_t n, uint8_t* out_) : HostW(in, n, out_) {}
+  uint32_t* table() { return tab32; }
+  uint32_t* scratch() { return scr; }
+  void begin_dyn() {
+    memset(tab32, 0, sizeof(tab32));
+    memset(lm, 0, sizeof(lm));
+    memset(tm, 0, sizeof(tm));
+    nmatch = 0;
+  }
+  template <bool EMIT>
+  void note(uint64_t lits, uint64_t take, uint32_t q) {
+    for (uint32_t l = 0; l < cnt; ++l) {
+      if ((lits >> l) & 1) {
+        ++tab32[rd.in[p0 + l]];
+      } else if ((take >> l) & 1) {
+        uint32_t eb, ev;
+        ++tab32[257 + len_sym(len[l], eb, ev)];
+        ++tab32[kLL + dist_sym(dist[l], eb, ev)];
+        if (EMIT) match[nmatch++] = (len[l] - 3) | (dist[l] << 8);
+      }
+    }
+    if (EMIT) {
+      const uint32_t w = q >> 6, sh = q & 63;
+      lm[w] |= lits << sh, tm[w] |= take << sh;
+      if (sh) lm[w + 1] |= lits >> (64 - sh), tm[w + 1] |= take >> (64 - sh);
+    }
+  }
+  template <bool EMIT, class F>
+  uint32_t emit_n(uint32_t n, uint64_t bit, F f) {
+    uint32_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      uint32_t nb = 0;
+      const uint32_t code = f(i, nb);
+      if (EMIT && nb) or_bits(bit + total, code);
+      total += nb;
+    }
+    return total;
+  }
+  void scratch_done() {}
+  uint32_t replay(uint64_t rs, uint32_t rl, uint64_t bit) {
+    uint32_t total = 0, k = 0;
+    for (uint32_t i = 0; i < rl; ++i) {
+      if ((lm[i >> 6] >> (i & 63)) & 1) {
+        uint32_t nb;
+        const uint32_t code = dyn_lit(tab32, rd.in[rs + i], nb);
+        or_bits(bit + total, code);
+        total += nb;
+      } else if ((tm[i >> 6] >> (i & 63)) & 1) {
+        const uint32_t m = match[k++];
+        uint32_t c1, n1, c2, n2;
+        dyn_match(tab32, (m & 0xffu) + 3, m >> 8, c1, n1, c2, n2);
+        or_bits(bit + total, c1);
+        or_bits(bit + total + n1, c2);
+        total += n1 + n2;
+      }
+    }
+    return total;
+  }
+};
+
+template <class W, bool DYN>
+int run(const uint8_t* in, uint64_t n, uint32_t maxd, uint8_t* out, uint64_t cap, uint64_t* out_len) {
+  uint64_t need;
+  {
+    W w(in, n, nullptr);
+    if constexpr (DYN) need = deflate_dyn<false>(w, n, maxd);
+    else need = deflate<false>(w, n, maxd);
+  }
+  if (out_len) *out_len = need;
+  if (need > cap) return GEVWS_ERR_CAPACITY;
+  W w(in, n, out);
+  uint64_t got;
+  if constexpr (DYN) got = deflate_dyn<true>(w, n, maxd);
+  else got = deflate<true>(w, n, maxd);
+  return got == need ? GEVWS_OK : GEVWS_ERR_INVALID;  // (the two passes are one algorithm)
+}
+
 }  // namespace
 
 extern "C" uint64_t gevws_deflate_bound(uint64_t n) { return gevws_deflate::bound(n); }
 
-extern "C" int gevws_deflate_raw(const uint8_t* in, uint64_t n, int window_bits, uint8_t* out, uint64_t cap,
-                                 uint64_t* out_len) {
+extern "C" int gevws_deflate_raw_flags(const uint8_t* in, uint64_t n, int window_bits, uint32_t flags, uint8_t* out,
+                                       uint64_t cap, uint64_t* out_len) {
   if (out_len) *out_len = 0;
-  if ((n && !in) || (cap && !out) || n > 0xFFFFFFFFull || (window_bits != 0 && (window_bits < 8 || window_bits > 15)))
+  if ((n && !in) || (cap && !out) || n > 0xFFFFFFFFull || (window_bits != 0 && (window_bits < 8 || window_bits > 15)) ||
+      (flags & ~GEVWS_DEFLATE_DYNAMIC))
     return GEVWS_ERR_INVALID;
   const uint32_t maxd = max_dist((uint32_t)window_bits);
-  uint64_t need;
-  {
-    HostW w(in, n, nullptr);
-    need = deflate<false>(w, n, maxd);
-  }
-  if (out_len) *out_len = need;
-  if (need > cap) return GEVWS_ERR_CAPACITY;
-  HostW w(in, n, out);
-  const uint64_t got = deflate<true>(w, n, maxd);
-  return got == need ? GEVWS_OK : GEVWS_ERR_INVALID;  // (the two passes are one algorithm)
+  if (flags & GEVWS_DEFLATE_DYNAMIC) return run<HostDynW, true>(in, n, maxd, out, cap, out_len);
+  return run<HostW, false>(in, n, maxd, out, cap, out_len);
+}
+
+extern "C" int gevws_deflate_raw(const uint8_t* in, uint64_t n, int window_bits, uint8_t* out, uint64_t cap,
+                                 uint64_t* out_len) {
+  return gevws_deflate_raw_flags(in, n, window_bits, 0, out, cap, out_len);
 }

@@ -627,7 +627,8 @@ int gevws_deflate_negotiate(const uint8_t *offer, uint64_t n, uint8_t *out, uint
  * blocks with BFINAL 0, closed by an empty stored block whose last four bytes
  * 00 00 ff ff are taken off; an empty message is the single byte 00.  Blocks
  * are fixed-Huffman (BTYPE 01) with LZ77 matches of length 3..258, or stored
- * (BTYPE 00) wherever that is smaller; no dynamic codes.  No match distance
+ * (BTYPE 00) wherever that is smaller; no dynamic codes unless the call asks
+ * for them (GEVWS_DEFLATE_DYNAMIC below).  No match distance
  * exceeds 2^window_bits (0 stands for 15), so an answer that carried
  * server_max_window_bits=N is honoured with window_bits = N.  Every message
  * starts from an empty window: server_no_context_takeover, which
@@ -645,6 +646,24 @@ int gevws_deflate_negotiate(const uint8_t *offer, uint64_t n, uint8_t *out, uint
  * a message with c >= length goes out plain: rsv 0, its bytes verbatim (RFC
  * 7692 section 6 leaves the choice to the sender, message by message).
  *
+ * GEVWS_DEFLATE_DYNAMIC in `flags`.  Every 4 KiB of input (a run) becomes a
+ * stored, fixed or dynamic-Huffman block (BTYPE 10), whichever ends at the
+ * lowest bit; on a tie stored wins, then fixed.  The matches, the runs and
+ * window_bits are as without the flag: a run's tokens are the same, only
+ * their coding differs, and all three ends are known before a bit is written.
+ * A stored or fixed block ends no later the earlier it starts, so a payload
+ * with the flag is never longer than without it; gevws_deflate_bound holds
+ * unchanged, and GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER compares against the
+ * length with dynamic blocks.  A dynamic block's code comes from the run's
+ * counts of the 286 literal / length symbols (end-of-block once) and the 30
+ * distance symbols: code lengths of at most 15 bits, canonical codes (RFC 1951
+ * section 3.2.2), HLIT / HDIST / HCLEN trimmed, the lengths run-length coded
+ * with 16 / 17 / 18 (literal / length and distance lengths apart), the
+ * code-length code of at most 7 bits.  A run without a match sends one
+ * distance code of one bit.  The construction is one integer function of the
+ * counts, ties broken by symbol index, shared by the device and
+ * gevws_deflate_raw_flags.  Without the flag every byte is as before.
+ *
  * d_summary: frames = records written, payload_bytes = bytes of d_out used,
  * payload_len = the sum of the wire payload lengths, errors 0.  status
  * GEVWS_ERR_CAPACITY when out_cap is too small: payload_bytes then holds the
@@ -654,6 +673,7 @@ int gevws_deflate_negotiate(const uint8_t *offer, uint64_t n, uint8_t *out, uint
  * range outside d_src[0, src_bytes), a length above 2^32 - 1: errors then
  * counts such records, the other fields are zero and nothing else is written. */
 #define GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER 1u     /* call flag */
+#define GEVWS_DEFLATE_DYNAMIC 2u                  /* call flag: dynamic-Huffman blocks where they are smaller */
 typedef struct gevws_deflate_msg {   /* 24 bytes: one message to send */
     uint64_t payload_off;   /* into d_src, a multiple of GEVWS_PAYLOAD_ALIGN */
     uint64_t length;        /* plain bytes, <= 2^32 - 1 */
@@ -682,6 +702,13 @@ int gevws_deflate_async(gevws_ctx *ctx, void *stream,
  * *out_len = the payload's length. */
 int gevws_deflate_raw(const uint8_t *in, uint64_t n, int window_bits,
                       uint8_t *out, uint64_t cap, uint64_t *out_len);
+
+/* gevws_deflate_raw with the call's flags: GEVWS_DEFLATE_DYNAMIC gives the
+ * payload gevws_deflate_async writes with that flag, 0 is gevws_deflate_raw
+ * bit for bit; any other bit (GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER too: the
+ * caller compares *out_len with n) is GEVWS_ERR_INVALID. */
+int gevws_deflate_raw_flags(const uint8_t *in, uint64_t n, int window_bits, uint32_t flags,
+                            uint8_t *out, uint64_t cap, uint64_t *out_len);
 
 /* Measurement helper, not on the reference path: n bytes (n % 16 == 0, d_dst
  * 16-byte aligned, d_src any alignment) copied with the unmask kernel's

@@ -13,7 +13,14 @@ distinct payloads.  The decode and the deflate step alternate in one process;
 the deflate step is timed by HIP events around its launches.  One JSON line
 per (shape, payload), medians over the rounds.
 
-    python tools/bench_deflate.py [--rounds 7] [--warmup 2] [--shapes many,large] [--out FILE]
+--dynamic adds a leg with GEVWS_DEFLATE_DYNAMIC (dynamic-Huffman blocks where
+they are smaller): the same shapes and payloads, the fixed-mode step and the
+dynamic-mode step alternating in the same rounds, and a second line per case
+with "mode": "dynamic" that carries the fixed-mode step of the same process
+beside it and the sizes against both zlib yardsticks.
+
+    python tools/bench_deflate.py [--rounds 7] [--warmup 2] [--shapes many,large] [--dynamic] [--commit ID]
+                                  [--out FILE]
 """
 from __future__ import annotations
 
@@ -79,6 +86,8 @@ def main():
     ap.add_argument("--shapes", default="many,large")
     ap.add_argument("--kinds", default="text,random")
     ap.add_argument("--no-cpu", action="store_true", help="skip the zlib baselines")
+    ap.add_argument("--dynamic", action="store_true", help="also time the step with GEVWS_DEFLATE_DYNAMIC")
+    ap.add_argument("--commit", default=None, help="recorded in every line")
     ap.add_argument("--out", default=None, help="append the lines to this file too")
     args = ap.parse_args()
     import numpy as np
@@ -133,58 +142,74 @@ def main():
         def decode():
             eng.decode_async(arena, in_bytes, conns, n, out, n, n * size)
 
-        def deflate():
-            eng.deflate_async(d_rec, n, None, src, src_bytes, 0, d_frames, d_out, out_cap, dsum)
+        def deflate(flags=0):
+            eng.deflate_async(d_rec, n, None, src, src_bytes, flags, d_frames, d_out, out_cap, dsum)
 
-        for _ in range(args.warmup):
-            decode(), deflate()
-        torch.cuda.synchronize()
-        s = dsum.cpu().numpy().view(gev_amd.SUMMARY_DTYPE)[0]
-        assert (int(s["status"]), int(s["frames"]), int(s["errors"])) == (0, n, 0), s
-        comp_bytes = int(s["payload_len"])
-        fr = d_frames.cpu().numpy().reshape(-1).view(gev_amd.OUT_FRAME_DTYPE)
-        for i in (0, 1, DISTINCT - 1, n - 1):  # the payloads inflate to the messages
-            o, c = int(fr["payload_off"][i]), int(fr["payload_len"][i])
-            p = d_out[o:o + c].cpu().numpy().tobytes()
-            assert zlib.decompressobj(-15).decompress(p + TAIL) == plains[i % DISTINCT], i
-        t_def, t_unmask = [], []
-        eng.set_timing(True)
-        for _ in range(args.rounds):  # the two alternate
-            decode()
-            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            e[0].record()
-            deflate()
-            e[1].record()
+        def checked(flags):
+            """The step's compressed bytes after a run whose payloads inflate to the messages."""
+            deflate(flags)
             torch.cuda.synchronize()
+            s = dsum.cpu().numpy().view(gev_amd.SUMMARY_DTYPE)[0]
+            assert (int(s["status"]), int(s["frames"]), int(s["errors"])) == (0, n, 0), s
+            fr = d_frames.cpu().numpy().reshape(-1).view(gev_amd.OUT_FRAME_DTYPE)
+            for i in (0, 1, DISTINCT - 1, n - 1):
+                o, c = int(fr["payload_off"][i]), int(fr["payload_len"][i])
+                p = d_out[o:o + c].cpu().numpy().tobytes()
+                assert zlib.decompressobj(-15).decompress(p + TAIL) == plains[i % DISTINCT], i
+            return int(s["payload_len"])
+
+        modes = [("fixed", 0)] + ([("dynamic", gev_amd.DEFLATE_DYNAMIC)] if args.dynamic else [])
+        for _ in range(args.warmup):
+            decode()
+            for _, flags in modes:
+                deflate(flags)
+        comp = {name: checked(flags) for name, flags in modes}
+        t_def, t_unmask = {name: [] for name, _ in modes}, []
+        eng.set_timing(True)
+        for _ in range(args.rounds):  # the decode and the step's modes alternate
+            decode()
+            for name, flags in modes:
+                e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                e[0].record()
+                deflate(flags)
+                e[1].record()
+                torch.cuda.synchronize()
+                t_def[name].append(e[0].elapsed_time(e[1]))
             ms, calls = eng.timing()
             assert calls == 1
-            t_def.append(e[0].elapsed_time(e[1]))
             t_unmask.append(ms[3])
         eng.set_timing(False)
-        m, u = median(t_def), median(t_unmask)
-        line = {
-            "path": "deflate step (permessage-deflate outbound, one wave per message, compressed twice: size, emit)",
-            "shape": shape, "payload": kind, "messages": n, "message_bytes": size, "plain_bytes": n * size,
-            "compressed_bytes": comp_bytes, "ratio": round(comp_bytes / (n * size), 4),
-            "deflate_ms": round(m, 4), "deflate_rounds_ms": [round(t, 4) for t in t_def],
-            "deflate_in_GBps": round(n * size / m / 1e6, 2), "deflate_out_GBps": round(comp_bytes / m / 1e6, 2),
-            "unmask_ms": round(u, 4), "unmask_rounds_ms": [round(t, 4) for t in t_unmask],
-            "unmask_read_plus_write_GBps": round(2 * n * size / u / 1e6, 1),
-            "rounds": args.rounds, "warmup": args.warmup}
-        for name, c in cpu.items():
-            line[f"{name}_bytes"] = c["bytes"]
-            line[f"size_vs_{name}"] = round(comp_bytes / c["bytes"], 4)
-            if "one" in c:
-                line.update({f"{name}_1core_ms": round(c["one"] * 1e3, 2),
-                             f"{name}_1core_in_GBps": round(n * size / c["one"] / 1e9, 3),
-                             f"{name}_16proc_ms": round(c["p16"] * 1e3, 2),
-                             f"{name}_16proc_in_GBps": round(n * size / c["p16"] / 1e9, 3)})
-        text_line = json.dumps(line)
-        print(text_line, flush=True)
-        if args.out:
-            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-            with open(args.out, "a") as f:
-                f.write(text_line + "\n")
+        u = median(t_unmask)
+        for name, _ in modes:
+            m, comp_bytes = median(t_def[name]), comp[name]
+            line = {
+                "path": "deflate step (permessage-deflate outbound, one wave per message, compressed twice: size, emit)",
+                "mode": name, "commit": args.commit,
+                "shape": shape, "payload": kind, "messages": n, "message_bytes": size, "plain_bytes": n * size,
+                "compressed_bytes": comp_bytes, "ratio": round(comp_bytes / (n * size), 4),
+                "deflate_ms": round(m, 4), "deflate_rounds_ms": [round(t, 4) for t in t_def[name]],
+                "deflate_in_GBps": round(n * size / m / 1e6, 2), "deflate_out_GBps": round(comp_bytes / m / 1e6, 2),
+                "unmask_ms": round(u, 4), "unmask_rounds_ms": [round(t, 4) for t in t_unmask],
+                "unmask_read_plus_write_GBps": round(2 * n * size / u / 1e6, 1),
+                "rounds": args.rounds, "warmup": args.warmup}
+            if name != "fixed":  # the fixed-mode step of the same process beside it
+                f = median(t_def["fixed"])
+                line.update({"fixed_deflate_ms": round(f, 4), "fixed_compressed_bytes": comp["fixed"],
+                             "time_vs_fixed": round(m / f, 4), "size_vs_fixed": round(comp_bytes / comp["fixed"], 4)})
+            for zname, c in cpu.items():
+                line[f"{zname}_bytes"] = c["bytes"]
+                line[f"size_vs_{zname}"] = round(comp_bytes / c["bytes"], 4)
+                if "one" in c:
+                    line.update({f"{zname}_1core_ms": round(c["one"] * 1e3, 2),
+                                 f"{zname}_1core_in_GBps": round(n * size / c["one"] / 1e9, 3),
+                                 f"{zname}_16proc_ms": round(c["p16"] * 1e3, 2),
+                                 f"{zname}_16proc_in_GBps": round(n * size / c["p16"] / 1e9, 3)})
+            text_line = json.dumps(line)
+            print(text_line, flush=True)
+            if args.out:
+                os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+                with open(args.out, "a") as f:
+                    f.write(text_line + "\n")
         del src, d_out, d_frames, arena, out
         torch.cuda.empty_cache()
     eng.close()
