@@ -26,6 +26,7 @@ from . import _abi
 from ._abi import (MSG_BEGIN, MSG_END, MSG_ERR_CONTINUATION, MSG_ERR_CONTROL, MSG_ERR_INTERLEAVE, MSG_ERR_OPCODE,
                    MSG_ERR_RSV, MSG_ERR_UTF8, MSG_OK)
 from ._abi import EXT_DEFLATE, INF_DONE, INF_PENDING, MSG_COMPRESSED, MSG_ERR_DEFLATE, MSG_ERR_TOO_BIG
+from ._abi import EXT_CLIENT_TAKEOVER, INF_CTX_BYTES, NEGOTIATE_CLIENT_TAKEOVER
 from ._abi import DEFLATE_DYNAMIC, DEFLATE_PLAIN_IF_NOT_SMALLER
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
@@ -87,6 +88,38 @@ def inflate_raw(b: bytes, cap: int) -> Tuple[int, bytes]:
     if st < 0:
         raise RuntimeError(f"gevws_inflate_raw: {status_string(st)}")
     return st, out.raw[: n.value]
+
+
+def inflate_raw_ctx(b: bytes, cap: int, ctx: bytearray) -> Tuple[int, bytes]:
+    """gevws_inflate_raw_ctx: inflate_raw over one connection's context slot
+    (a bytearray of INF_CTX_BYTES, zeroed for a fresh connection, updated in
+    place): the message is inflated behind the slot's window and appended to
+    it; a failure marks the slot broken."""
+    b = bytes(b)
+    if not isinstance(ctx, bytearray) or len(ctx) != INF_CTX_BYTES:
+        raise ValueError("ctx: a bytearray of INF_CTX_BYTES")
+    out = ctypes.create_string_buffer(max(cap, 1))
+    n = ctypes.c_uint64(0)
+    slot = (ctypes.c_uint8 * INF_CTX_BYTES).from_buffer(ctx)
+    st = lib.gevws_inflate_raw_ctx(ctypes.c_char_p(b), len(b), out, cap, ctypes.byref(n), slot)
+    if st < 0:
+        raise RuntimeError(f"gevws_inflate_raw_ctx: {status_string(st)}")
+    return st, out.raw[: n.value]
+
+
+def deflate_negotiate_ext(value: bytes, flags: int = 0) -> Tuple[bytes, int]:
+    """gevws_deflate_negotiate_flags: (the answer, the connection's conn_ext
+    byte).  With NEGOTIATE_CLIENT_TAKEOVER the client may keep its window
+    unless its offer said otherwise: the byte then carries EXT_CLIENT_TAKEOVER."""
+    value = bytes(value)
+    out = ctypes.create_string_buffer(256)
+    n = ctypes.c_uint64(0)
+    ext = ctypes.c_uint8(0)
+    st = lib.gevws_deflate_negotiate_flags(ctypes.c_char_p(value), len(value), flags, out, len(out), ctypes.byref(n),
+                                           ctypes.byref(ext))
+    if st != OK:
+        raise RuntimeError(f"gevws_deflate_negotiate_flags: {status_string(st)}")
+    return out.raw[: n.value], int(ext.value)
 
 
 def deflate_bound(n: int) -> int:
@@ -567,12 +600,31 @@ class Engine:
         if st != OK:
             raise RuntimeError(f"gevws_inflate_async: {status_string(st)}")
 
+    def inflate_ctx_async(self, frames, max_frames: int, messages, max_messages: int, msg_of, msg_summary, payload,
+                          max_message_bytes: int, state, inflated, out, out_cap: int, summary, conn_ext, contexts,
+                          n_conns: int, stream=None) -> None:
+        """gevws_inflate_ctx_async: inflate_async with client context takeover
+        -- conn_ext: uint8 [n_conns] (EXT_DEFLATE | EXT_CLIENT_TAKEOVER),
+        contexts: uint8 [n_conns, INF_CTX_BYTES], zeroed for fresh connections
+        and carried from pass to pass.  Either None is inflate_async."""
+        st = lib.gevws_inflate_ctx_async(
+            self._ctx, _stream_handle(stream), frames.data_ptr(), max_frames, messages.data_ptr(), max_messages,
+            msg_of.data_ptr(), msg_summary.data_ptr(), payload.data_ptr(), max_message_bytes,
+            state.data_ptr() if state is not None else None, inflated.data_ptr(), out.data_ptr(), out_cap,
+            summary.data_ptr(), conn_ext.data_ptr() if conn_ext is not None else None,
+            contexts.data_ptr() if contexts is not None else None, n_conns)
+        if st != OK:
+            raise RuntimeError(f"gevws_inflate_ctx_async: {status_string(st)}")
+
     def inflate(self, out: "Batch", msgs: "Messages", max_message_bytes: int, state=None,
-                out_cap: Optional[int] = None, stream=None) -> "Inflated":
+                out_cap: Optional[int] = None, stream=None, conn_ext=None, contexts=None) -> "Inflated":
         """The inflate step behind Engine.messages(out, conn_ext=...): every
         whole compressed message of the pass inflated.  Grows the output once
         on ERR_CAPACITY (nothing is written and the state is untouched by the
-        call that did not fit)."""
+        call that did not fit).  With conn_ext and contexts (uint8 [n_conns,
+        INF_CTX_BYTES], the caller's, carried from pass to pass) connections
+        with EXT_CLIENT_TAKEOVER keep their window between messages; the call
+        that did not fit leaves the contexts untouched too."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n = int(msgs.summary_host()["frames"])
@@ -582,8 +634,14 @@ class Engine:
             res = Inflated(inflated=torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=dev),
                            out=torch.empty(max(out_cap, 16), dtype=torch.uint8, device=dev),
                            summary=torch.zeros(64, dtype=torch.uint8, device=dev), n_messages=n)
-            self.inflate_async(out.frames, msgs.n_frames, msgs.messages, n, msgs.msg_of, msgs.summary, out.payload,
-                               max_message_bytes, state, res.inflated, res.out, out_cap, res.summary, stream)
+            if conn_ext is not None and contexts is not None:
+                self.inflate_ctx_async(out.frames, msgs.n_frames, msgs.messages, n, msgs.msg_of, msgs.summary,
+                                       out.payload, max_message_bytes, state, res.inflated, res.out, out_cap,
+                                       res.summary, conn_ext, contexts, int(contexts.shape[0]), stream)
+            else:
+                self.inflate_async(out.frames, msgs.n_frames, msgs.messages, n, msgs.msg_of, msgs.summary,
+                                   out.payload, max_message_bytes, state, res.inflated, res.out, out_cap,
+                                   res.summary, stream)
             torch.cuda.synchronize(self.device)
             s = res.summary_host()
             if int(s["status"]) == ERR_CAPACITY and attempt == 0:

@@ -70,6 +70,9 @@ MSG_COMPRESSED = 4
 DEFLATE_PLAIN_IF_NOT_SMALLER = 1  # gevws_deflate_async flag
 DEFLATE_DYNAMIC = 2  # gevws_deflate_async / gevws_deflate_raw_flags flag
 EXT_DEFLATE = 1
+EXT_CLIENT_TAKEOVER = 2  # conn_ext bit: the client keeps its window (gevws_inflate_ctx_async)
+INF_CTX_BYTES = 32768 + 64  # one connection's slot of d_inf_ctx
+NEGOTIATE_CLIENT_TAKEOVER = 1  # gevws_deflate_negotiate_flags flag
 INF_DONE = 1
 INF_PENDING = 2
 
@@ -269,6 +272,12 @@ SIGNATURES = {
     "gevws_inflate_raw": (ctypes.c_int, [P, ctypes.c_uint64, P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "gevws_deflate_negotiate": (ctypes.c_int, [P, ctypes.c_uint64, P, ctypes.c_uint64,
                                                ctypes.POINTER(ctypes.c_uint64)]),
+    "gevws_inflate_ctx_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, P, P, P, ctypes.c_uint64,
+                                               P, P, P, ctypes.c_uint64, P, P, P, ctypes.c_uint32]),
+    "gevws_inflate_raw_ctx": (ctypes.c_int, [P, ctypes.c_uint64, P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                             P]),
+    "gevws_deflate_negotiate_flags": (ctypes.c_int, [P, ctypes.c_uint64, ctypes.c_uint32, P, ctypes.c_uint64,
+                                                     ctypes.POINTER(ctypes.c_uint64), P]),
     "gevws_deflate_bound": (ctypes.c_uint64, [ctypes.c_uint64]),
     "gevws_deflate_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, ctypes.c_uint64, ctypes.c_uint32, P, P,
                                            ctypes.c_uint64, P]),

@@ -14,6 +14,14 @@
 //                  of gevws_utf8.hpp over the finished output
 //   k_inf_state    one lane per connection's first message: d_state.failed
 //
+// gevws_inflate_ctx_async (client context takeover) launches k_inf_size<true>
+// and k_inf_emit<true>, and k_inf_verdict between the scan and the emit.  They
+// serve both kinds of connection with a wave-uniform branch: a connection
+// without the takeover bit runs the code above; a takeover connection's
+// messages are a chain that one wave decodes in order, the window carried in
+// the connection's slot of d_inf_ctx (see "context takeover" below).  The
+// <false> instances are the kernels of gevws_inflate_async, unchanged.
+//
 // A wave's decode state -- bit buffer, counters, each Huffman code's limits --
 // is the same in every lane; the lanes differ only where bytes move: the 1 KiB
 // refills of the input (hopping from fragment to fragment), match copies,
@@ -166,21 +174,47 @@ struct InfSizeIo : InfSource {  // counts only: the core keeps the count
   __device__ __forceinline__ uint64_t stored(uint64_t want) { return skip(want); }
 };
 
+// CTX: a message of a context-takeover chain.  The window is the connection's
+// ring -- stream byte i at win[i % kInfWin] -- and the message starts in it at
+// `start`, the connection's stream position, which is not 16-aligned in
+// general; pos and flushed are stream positions too, so a distance reaches
+// back over the message boundary without a seam.  The message's byte j still
+// goes to out[j], on a 16-byte boundary: the flush realigns.
+template <bool CTX>
 struct InfEmitIo : InfSource {
   uint8_t* win;  // LDS, kInfWin bytes: byte i of the output at win[i % kInfWin]
   uint8_t* out;  // the message's bytes in d_out (16-byte aligned)
   uint64_t pos = 0, flushed = 0;
+  uint64_t start = 0;
 
   __device__ InfEmitIo(const gevws_frame* fr_, const int64_t* msg_of_, const uint8_t* payload_, uint8_t* inbuf_,
-                       uint64_t m_, const gevws_message& msg, uint64_t max_frames_, uint8_t* win_, uint8_t* out_)
-      : InfSource(fr_, msg_of_, payload_, inbuf_, m_, msg, max_frames_), win(win_), out(out_) {}
+                       uint64_t m_, const gevws_message& msg, uint64_t max_frames_, uint8_t* win_, uint8_t* out_,
+                       uint64_t start_ = 0)
+      : InfSource(fr_, msg_of_, payload_, inbuf_, m_, msg, max_frames_), win(win_), out(out_) {
+    if constexpr (CTX) pos = flushed = start = start_;
+  }
 
+  // The 16 bytes of the window from stream position x on.  CTX: x = start mod
+  // 16 for every vector of the message, so two aligned reads and a byte shift.
+  __device__ __forceinline__ u32x4 window16(uint64_t x) const {
+    if constexpr (CTX) {
+      const uint32_t a = (uint32_t)x & ~15u;
+      return funnel16(*reinterpret_cast<const u32x4*>(win + (a & (kInfWin - 1))),
+                      *reinterpret_cast<const u32x4*>(win + ((a + 16) & (kInfWin - 1))), uniform32((uint32_t)start & 15));
+    } else {
+      return *reinterpret_cast<const u32x4*>(win + (x & (kInfWin - 1)));
+    }
+  }
+  __device__ __forceinline__ uint64_t rel() const {  // `flushed` as an offset into the message
+    if constexpr (CTX) return flushed - start;
+    else return flushed;
+  }
   // Whole KiB of the window to d_out.  At most 1 023 + 1 024 bytes are ever
   // unflushed, so nothing unflushed is overwritten 32 KiB later.
   __device__ __forceinline__ void flush() {
     while (pos - flushed >= kInfIn) {
-      const u32x4 v = *reinterpret_cast<const u32x4*>(win + ((flushed + 16 * lane) & (kInfWin - 1)));
-      *reinterpret_cast<u32x4*>(out + flushed + 16 * lane) = v;
+      const u32x4 v = window16(flushed + 16 * lane);
+      *reinterpret_cast<u32x4*>(out + rel() + 16 * lane) = v;
       flushed += kInfIn;
     }
   }
@@ -189,9 +223,9 @@ struct InfEmitIo : InfSource {
     flush();
     const uint64_t r = pos - flushed, o = 16 * (uint64_t)lane;
     if (o < r) {
-      u32x4 v = *reinterpret_cast<const u32x4*>(win + ((flushed + o) & (kInfWin - 1)));
+      u32x4 v = window16(flushed + o);
       if (r - o < 16) v = keep_bytes(v, (int64_t)(r - o));
-      *reinterpret_cast<u32x4*>(out + flushed + o) = v;
+      *reinterpret_cast<u32x4*>(out + rel() + o) = v;
     }
   }
   __device__ __forceinline__ void put(uint32_t b) {
@@ -240,18 +274,121 @@ __device__ __forceinline__ bool inf_wanted(const gevws_message& msg) {
   return (msg.flags & all) == all;
 }
 
+// ------------------------------------------------------------------ context takeover
+// A takeover connection's compressed messages depend on each other in order
+// (message k's window is the output of the messages before it), so the wave of
+// the connection's first message in the batch walks all of them, one after
+// another, and the waves of its other messages exit: the data dependency of
+// context takeover, in both passes.  The slot (include/gevws.h): a 64-byte
+// head, then the ring image.
+constexpr uint32_t kCtxHead = GEVWS_INF_CTX_BYTES - kInfWin;
+constexpr uint64_t kInfInvalid = 1ull << 32;  // in blk field 3: a record with conn >= n_conns
+static_assert(kCtxHead == 64 && GEVWS_INF_CTX_BYTES % 16 == 0, "slots and their rings lie on 16-byte boundaries");
+
+// The message of a workgroup.  Workgroups are dealt round-robin over the 8
+// XCDs (and within one over its CUs), and a chain's work sits in its first
+// message's workgroup: with a regular number of messages a connection (8,
+// say) the identity puts every chain on the same XCD -- measured, DESIGN
+// section 5.6.  So with contexts the grid is kInfSpread x q workgroups and
+// workgroup b takes message (b % kInfSpread) q + b / kInfSpread: consecutive
+// workgroups take messages q apart, and q is a multiple of 16 (inf_grid_q),
+// so chains of a period that divides 16 have their heads in runs of
+// kInfSpread consecutive workgroups, which fill the device evenly, and any
+// other period has no common factor with the hardware's powers of two.
+constexpr uint32_t kInfSpread = 1024;
+inline uint32_t inf_grid_q(uint32_t nm) {
+  const uint32_t q = (nm + kInfSpread - 1) / kInfSpread;
+  return q <= 8 ? q : (q + 15) / 16 * 16;  // (up to 8 192 messages the grid is nearly resident anyway)
+}
+template <bool CTX>
+__device__ __forceinline__ uint64_t inf_block_message() {
+  if constexpr (CTX) return (uint64_t)(blockIdx.x % kInfSpread) * (gridDim.x / kInfSpread) + blockIdx.x / kInfSpread;
+  else return blockIdx.x;
+}
+
+__device__ __forceinline__ void inf_size_record(uint64_t k, const InfRec& r, uint64_t* __restrict__ blk,
+                                                InfRec* __restrict__ rec) {
+  rec[k] = r;
+  if (r.flags == GEVWS_INF_DONE) {
+    const bool ok = r.status == GEVWS_MSG_OK;
+    blk[k * kBlkFields + 0] = ok ? 1 : 0;
+    blk[k * kBlkFields + 1] = round16(r.len);
+    blk[k * kBlkFields + 2] = r.len;
+    blk[k * kBlkFields + 3] = ok ? 0 : 1;
+  }
+}
+
+// The sizing pass over connection c's messages from m on: needs no window
+// bytes, only the slot's head; the history length runs through the chain in
+// registers.  Writes the records, nothing to the slot.
+__device__ __forceinline__ void inf_size_chain(const gevws_frame* __restrict__ fr, uint64_t max_frames,
+                                               const gevws_message* __restrict__ msgs, uint64_t n, uint64_t m,
+                                               uint32_t c, const int64_t* __restrict__ msg_of,
+                                               const uint8_t* __restrict__ payload, uint64_t limit,
+                                               const uint8_t* __restrict__ slot, uint8_t* s_in,
+                                               gevws_inflate::Tables& s_tab, uint64_t* __restrict__ blk,
+                                               InfRec* __restrict__ rec) {
+  const uint64_t total = uniform64(*reinterpret_cast<const uint64_t*>(slot));
+  uint32_t hist = total < kInfWin ? (uint32_t)total : kInfWin;
+  uint32_t broken = uniform32(slot[8]);
+  bool stopped = false;
+  for (uint64_t k = m; k < n; ++k) {  // (at most the connection's messages in the batch)
+    const gevws_message msg = msgs[k];
+    if (uniform32(msg.conn) != c) break;
+    if (!(uniform32(msg.flags) & GEVWS_MSG_COMPRESSED)) continue;  // not in the window
+    InfRec r;
+    r.len = 0, r.status = GEVWS_MSG_OK, r.flags = GEVWS_INF_PENDING, r.pad = 0;
+    if (broken) {  // the context is lost: the first failure's status, nothing decoded
+      r.status = (uint8_t)broken, r.flags = GEVWS_INF_DONE;
+    } else if (stopped || !inf_wanted(msg)) {
+      stopped = true;  // not whole in the batch: the chain stops here
+    } else {
+      uint64_t len = 0;
+      InfSizeIo io(fr, msg_of, payload, s_in, k, msg, max_frames);
+      r.status = (uint8_t)gevws_inflate::inflate(io, s_tab, limit, &len, hist);
+      r.flags = GEVWS_INF_DONE;
+      if (r.status != GEVWS_MSG_OK) {
+        broken = r.status;
+      } else {
+        r.len = (uint32_t)len;
+        hist = len + hist < kInfWin ? (uint32_t)len + hist : kInfWin;
+      }
+    }
+    if (threadIdx.x == 0) inf_size_record(k, r, blk, rec);
+  }
+}
+
 // ------------------------------------------------------------------ 1. sizes and verdicts
+// CTX: contexts are given (gevws_inflate_ctx_async); <false> is the kernel of
+// gevws_inflate_async.
+template <bool CTX>
 __global__ __launch_bounds__(kInfBlock) void k_inf_size(const gevws_frame* __restrict__ fr, uint64_t max_frames,
                                                         const gevws_message* __restrict__ msgs,
                                                         uint64_t max_messages, const int64_t* __restrict__ msg_of,
                                                         const gevws_summary* __restrict__ gate,
                                                         const uint8_t* __restrict__ payload, uint64_t limit,
-                                                        uint64_t* __restrict__ blk, InfRec* __restrict__ rec) {
+                                                        uint64_t* __restrict__ blk, InfRec* __restrict__ rec,
+                                                        const uint8_t* __restrict__ conn_ext,
+                                                        const uint8_t* __restrict__ inf_ctx, uint32_t n_conns) {
   __shared__ __attribute__((aligned(16))) uint8_t s_in[kInfIn];
   __shared__ gevws_inflate::Tables s_tab;
-  const uint64_t m = blockIdx.x;
-  if (m >= gated_count(max_messages, gate)) return;  // (blk and rec are zeroed)
+  const uint64_t m = inf_block_message<CTX>();
+  const uint64_t n = gated_count(max_messages, gate);
+  if (m >= n) return;  // (blk and rec are zeroed)
   const gevws_message msg = msgs[m];
+  if constexpr (CTX) {
+    const uint32_t c = uniform32(msg.conn);
+    if (c >= n_conns) {  // never an index: the call is GEVWS_ERR_INVALID (k_inf_verdict)
+      if (threadIdx.x == 0) blk[m * kBlkFields + 3] = kInfInvalid;
+      return;
+    }
+    if (uniform32(conn_ext[c]) & GEVWS_EXT_CLIENT_TAKEOVER) {  // wave-uniform
+      if (m && uniform32(msgs[m - 1].conn) == c) return;  // the connection's first message walks its messages
+      inf_size_chain(fr, max_frames, msgs, n, m, c, msg_of, payload, limit,
+                     inf_ctx + (uint64_t)c * GEVWS_INF_CTX_BYTES, s_in, s_tab, blk, rec);
+      return;
+    }
+  }
   if (!(msg.flags & GEVWS_MSG_COMPRESSED)) return;
   InfRec r;
   r.len = 0, r.status = GEVWS_MSG_OK, r.flags = GEVWS_INF_PENDING, r.pad = 0;
@@ -275,7 +412,83 @@ __global__ __launch_bounds__(kInfBlock) void k_inf_size(const gevws_frame* __res
   }
 }
 
+// ------------------------------------------------------------------ 1b. a malformed record fails the call
+__global__ void k_inf_verdict(gevws_summary* __restrict__ sum) {
+  const uint64_t bad = sum->errors >> 32;
+  if (bad == 0) return;
+  gevws_summary s;
+  memset(&s, 0, sizeof(s));
+  s.errors = bad;
+  s.status = GEVWS_ERR_INVALID;
+  *sum = s;
+}
+
+// The emit pass over connection c's messages from m on, the only code that
+// writes a slot.  The slot's valid part goes into the LDS ring at its own
+// indices, the chain is decoded with the ring position running on across the
+// messages, and at the end the ring bytes this pass produced go back to the
+// slot with the head: the ring image in HBM already holds the older bytes.
+__device__ __forceinline__ void inf_emit_chain(const gevws_frame* __restrict__ fr, uint64_t max_frames,
+                                               const gevws_message* __restrict__ msgs, uint64_t n, uint64_t m,
+                                               uint32_t c, const int64_t* __restrict__ msg_of,
+                                               const uint8_t* __restrict__ payload,
+                                               const uint64_t* __restrict__ blk, const InfRec* __restrict__ rec,
+                                               uint8_t* slot, uint8_t* s_win, uint8_t* s_in,
+                                               gevws_inflate::Tables& s_tab, uint8_t* __restrict__ d_out) {
+  const uint32_t lane = threadIdx.x & 63;
+  // what the sizing pass decided for the chain
+  bool any = false;
+  uint32_t fail = 0;
+  for (uint64_t k = m; k < n && uniform32(msgs[k].conn) == c; ++k) {
+    const InfRec rk = rec[k];
+    if (uniform32(rk.flags) != GEVWS_INF_DONE) continue;
+    if (uniform32(rk.status) == GEVWS_MSG_OK) any = any || uniform32(rk.len) != 0;
+    else if (!fail) fail = uniform32(rk.status);
+  }
+  const uint32_t broken = uniform32(slot[8]);
+  if (!any && (fail == 0 || broken)) return;  // the slot stays as it is
+  const uint64_t total0 = uniform64(*reinterpret_cast<const uint64_t*>(slot));
+  uint64_t total = total0;
+  uint8_t* ring = slot + kCtxHead;
+  if (any) {
+    const uint32_t valid = total0 < kInfWin ? (uint32_t)round16(total0) : kInfWin;
+    for (uint32_t o = 16 * lane; o < valid; o += kInfIn)
+      *reinterpret_cast<u32x4*>(s_win + o) = *reinterpret_cast<const u32x4*>(ring + o);
+    wave_lds_order();
+    for (uint64_t k = m; k < n && uniform32(msgs[k].conn) == c; ++k) {
+      const InfRec rk = rec[k];
+      const uint32_t len_k = uniform32(rk.len);
+      // (after a failure or a stop nothing is DONE and OK any more)
+      if (uniform32(rk.flags) != GEVWS_INF_DONE || uniform32(rk.status) != GEVWS_MSG_OK || len_k == 0) continue;
+      const gevws_message msg = msgs[k];
+      InfEmitIo<true> io(fr, msg_of, payload, s_in, k, msg, max_frames, s_win,
+                         d_out + uniform64(blk[k * kBlkFields + 1]), total);
+      uint64_t len = 0;
+      // the sized length is the limit: the wave never writes past the message's allotted bytes
+      (void)gevws_inflate::inflate(io, s_tab, (uint64_t)len_k, &len, total < kInfWin ? (uint32_t)total : kInfWin);
+      io.finish();
+      total += len_k;
+    }
+    wave_lds_order();
+    // stream bytes [total0, total), at most the last 32 KiB of them, as whole
+    // vectors: their other bytes are the slot's own (loaded above), or zeros
+    // where the stream has not reached yet
+    uint64_t x = total - total0 >= kInfWin ? total - kInfWin : total0;
+    for (x = (x & ~15ull) + 16 * lane; x < total; x += kInfIn) {
+      const uint32_t o = (uint32_t)x & (kInfWin - 1);
+      u32x4 v = *reinterpret_cast<const u32x4*>(s_win + o);
+      if (total < kInfWin && total - x < 16) v = keep_bytes(v, (int64_t)(total - x));
+      *reinterpret_cast<u32x4*>(ring + o) = v;
+    }
+  }
+  if (lane == 0) {
+    *reinterpret_cast<uint64_t*>(slot) = total;
+    if (fail && !broken) slot[8] = (uint8_t)fail;
+  }
+}
+
 // ------------------------------------------------------------------ 2. the bytes
+template <bool CTX>
 __global__ __launch_bounds__(kInfBlock) void k_inf_emit(const gevws_frame* __restrict__ fr, uint64_t max_frames,
                                                         const gevws_message* __restrict__ msgs,
                                                         uint64_t max_messages, const int64_t* __restrict__ msg_of,
@@ -285,13 +498,15 @@ __global__ __launch_bounds__(kInfBlock) void k_inf_emit(const gevws_frame* __res
                                                         const InfRec* __restrict__ rec,
                                                         const gevws_summary* __restrict__ sum,
                                                         gevws_inflated* __restrict__ inflated,
-                                                        uint8_t* __restrict__ d_out) {
+                                                        uint8_t* __restrict__ d_out,
+                                                        const uint8_t* __restrict__ conn_ext, uint8_t* inf_ctx) {
   __shared__ __attribute__((aligned(16))) uint8_t s_win[kInfWin];
   __shared__ __attribute__((aligned(16))) uint8_t s_in[kInfIn];
   __shared__ gevws_inflate::Tables s_tab;
-  if (sum->status != GEVWS_OK) return;  // capacity: nothing written
-  const uint64_t m = blockIdx.x;
-  if (m >= gated_count(max_messages, gate)) return;
+  if (sum->status != GEVWS_OK) return;  // capacity: nothing written, the slots untouched
+  const uint64_t m = inf_block_message<CTX>();
+  const uint64_t n = gated_count(max_messages, gate);
+  if (m >= n) return;
   const InfRec r = rec[m];
   const uint64_t base = blk[m * kBlkFields + 1];  // (exclusive after the scan)
   if (threadIdx.x == 0) {
@@ -305,9 +520,18 @@ __global__ __launch_bounds__(kInfBlock) void k_inf_emit(const gevws_frame* __res
     }
     inflated[m] = o;
   }
+  if constexpr (CTX) {
+    const uint32_t c = uniform32(msgs[m].conn);  // (below n_conns, or the summary were INVALID)
+    if (uniform32(conn_ext[c]) & GEVWS_EXT_CLIENT_TAKEOVER) {  // wave-uniform
+      if (m && uniform32(msgs[m - 1].conn) == c) return;  // the connection's first message walks its messages
+      inf_emit_chain(fr, max_frames, msgs, n, m, c, msg_of, payload, blk, rec,
+                     inf_ctx + (uint64_t)c * GEVWS_INF_CTX_BYTES, s_win, s_in, s_tab, d_out);
+      return;
+    }
+  }
   if (r.flags != GEVWS_INF_DONE || r.status != GEVWS_MSG_OK || r.len == 0) return;
   const gevws_message msg = msgs[m];
-  InfEmitIo io(fr, msg_of, payload, s_in, m, msg, max_frames, s_win, d_out + base);
+  InfEmitIo<false> io(fr, msg_of, payload, s_in, m, msg, max_frames, s_win, d_out + base);
   uint64_t len = 0;
   // the sized length is the limit: the wave never writes past its allotted bytes
   (void)gevws_inflate::inflate(io, s_tab, (uint64_t)r.len, &len);
@@ -370,12 +594,16 @@ __global__ __launch_bounds__(kWalkBlock) void k_inf_state(const gevws_message* _
 
 using namespace gevws_impl;
 
-extern "C" int gevws_inflate_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames, uint64_t max_frames,
-                                   const gevws_message* d_messages, uint64_t max_messages, const int64_t* d_msg_of,
-                                   const gevws_summary* d_msg_summary, const uint8_t* d_payload,
-                                   uint64_t max_message_bytes, gevws_msg_state* d_state,
-                                   gevws_inflated* d_inflated, uint8_t* d_out, uint64_t out_cap,
-                                   gevws_summary* d_summary) {
+extern "C" int gevws_inflate_ctx_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames,
+                                       uint64_t max_frames, const gevws_message* d_messages, uint64_t max_messages,
+                                       const int64_t* d_msg_of, const gevws_summary* d_msg_summary,
+                                       const uint8_t* d_payload, uint64_t max_message_bytes, gevws_msg_state* d_state,
+                                       gevws_inflated* d_inflated, uint8_t* d_out, uint64_t out_cap,
+                                       gevws_summary* d_summary, const uint8_t* d_conn_ext, uint8_t* d_inf_ctx,
+                                       uint32_t n_conns) {
+  const bool with_ctx = d_conn_ext && d_inf_ctx;  // either NULL: gevws_inflate_async, bit for bit
+  if (with_ctx && ((reinterpret_cast<uintptr_t>(d_inf_ctx) & 15) || max_messages > 0x7FF00000ull))
+    return GEVWS_ERR_INVALID;
   if (!ctx || !d_summary || max_messages > 0x7FFFFFFFull || max_message_bytes < 1 ||
       max_message_bytes > 0xFFFFFFFFull)
     return GEVWS_ERR_INVALID;
@@ -394,11 +622,26 @@ extern "C" int gevws_inflate_async(gevws_ctx* ctx, void* stream, const gevws_fra
   const InfScratch s = inf_scratch(ctx->scratch, max_messages);
   GEVWS_HIP(hipMemsetAsync(ctx->scratch, 0, s.total, st));
   const uint32_t nm = (uint32_t)max_messages;
-  k_inf_size<<<nm, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of, d_msg_summary,
-                                       d_payload, max_message_bytes, s.blk, s.rec);
+  const uint32_t ng = kInfSpread * inf_grid_q(nm);  // the grid with contexts (inf_block_message)
+  if (with_ctx)
+    k_inf_size<true><<<ng, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of,
+                                               d_msg_summary, d_payload, max_message_bytes, s.blk, s.rec, d_conn_ext,
+                                               d_inf_ctx, n_conns);
+  else
+    k_inf_size<false><<<nm, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of,
+                                                d_msg_summary, d_payload, max_message_bytes, s.blk, s.rec, nullptr,
+                                                nullptr, 0);
   k_scan_blocks<false><<<1, kScanBlock, 0, st>>>(s.blk, nm, UINT64_MAX, out_cap, d_summary);
-  k_inf_emit<<<nm, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of, d_msg_summary,
-                                       d_payload, s.blk, s.rec, d_summary, d_inflated, d_out);
+  if (with_ctx) {
+    k_inf_verdict<<<1, 1, 0, st>>>(d_summary);
+    k_inf_emit<true><<<ng, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of,
+                                               d_msg_summary, d_payload, s.blk, s.rec, d_summary, d_inflated, d_out,
+                                               d_conn_ext, d_inf_ctx);
+  } else {
+    k_inf_emit<false><<<nm, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of,
+                                                d_msg_summary, d_payload, s.blk, s.rec, d_summary, d_inflated, d_out,
+                                                nullptr, nullptr);
+  }
   k_inf_utf8<<<(nm + kWalkBlock / 64 - 1) / (kWalkBlock / 64), kWalkBlock, 0, st>>>(d_messages, max_messages,
                                                                                    d_msg_summary, d_summary,
                                                                                    d_inflated, d_out);
@@ -407,4 +650,15 @@ extern "C" int gevws_inflate_async(gevws_ctx* ctx, void* stream, const gevws_fra
                                                                            d_summary, d_inflated, d_state);
   GEVWS_HIP(hipGetLastError());
   return mark_last(ctx, st);
+}
+
+extern "C" int gevws_inflate_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames, uint64_t max_frames,
+                                   const gevws_message* d_messages, uint64_t max_messages, const int64_t* d_msg_of,
+                                   const gevws_summary* d_msg_summary, const uint8_t* d_payload,
+                                   uint64_t max_message_bytes, gevws_msg_state* d_state,
+                                   gevws_inflated* d_inflated, uint8_t* d_out, uint64_t out_cap,
+                                   gevws_summary* d_summary) {
+  return gevws_inflate_ctx_async(ctx, stream, d_frames, max_frames, d_messages, max_messages, d_msg_of, d_msg_summary,
+                                 d_payload, max_message_bytes, d_state, d_inflated, d_out, out_cap, d_summary, nullptr,
+                                 nullptr, 0);
 }

@@ -10,6 +10,7 @@
 //   bool get(uint32_t& b)            the next byte of the stream S, false at its end
 //   void put(uint32_t b)             one output byte
 //   void copy(uint32_t d, uint32_t n)  n >= 1 bytes from d back, as a byte-serial copy
+//                                    (with a history, d may reach behind the message's first byte)
 //   uint64_t stored(uint64_t n)      up to n bytes from the source to the sink;
 //                                    returns how many there were
 // On the device every lane of the wave runs this code on the same values
@@ -19,8 +20,9 @@
 // Verdicts (include/gevws.h, gevws_inflate_async): a block that ends with
 // BFINAL set ends the stream, one that ends with less than a whole byte of S
 // unread ends it too (unless the bits left already spell block type 3);
-// running out of S anywhere else, a distance beyond the bytes produced and
-// everything zlib's inflate rejects are kErrDeflate; an output byte beyond
+// running out of S anywhere else, a distance beyond the bytes produced (plus
+// the history the caller vouches for) and everything zlib's inflate rejects
+// are kErrDeflate; an output byte beyond
 // `limit` is kErrTooBig.  Errors come in stream order, as from a byte-serial
 // decoder.  Every loop consumes at least one bit of S or produces at least one
 // byte, so the work is bounded by the length of S and by `limit`.
@@ -251,8 +253,12 @@ GEVWS_INF_HD bool dynamic_tables(Bits& b, Io& io, Tables& t, Code& lit, Code& di
 }
 
 // The whole stream.  *produced = bytes handed to the sink (at most limit).
+// `history` (at most 32 768) = the bytes of the connection's earlier messages
+// that lie before this one's first byte (context takeover): a distance may
+// reach that far behind the message, and the sink's copy() serves it.  zlib
+// counts the same way, so the check stays exact; 0 is a message on its own.
 template <class Io>
-GEVWS_INF_HD int inflate(Io& io, Tables& t, uint64_t limit, uint64_t* produced) {
+GEVWS_INF_HD int inflate(Io& io, Tables& t, uint64_t limit, uint64_t* produced, uint32_t history = 0) {
   Bits b;
   Code lcode, dcode;
   uint64_t out = 0;
@@ -340,7 +346,7 @@ GEVWS_INF_HD int inflate(Io& io, Tables& t, uint64_t limit, uint64_t* produced) 
           break;
         }
         dist = dist_base((uint32_t)d) + x;
-        if (dist > out) {
+        if (dist > out + history) {
           status = kErrDeflate;
           break;
         }

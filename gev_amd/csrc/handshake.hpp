@@ -43,6 +43,10 @@ class Upgrader {
 
 // The Sec-WebSocket-Extensions answer to the first permessage-deflate offer in
 // `offer` that needs no context takeover of the server; "" when there is none.
-std::string DeflateAnswer(const uint8_t* offer, uint64_t n);
+// With client_takeover the answer leaves client_no_context_takeover out unless
+// the offer carried it; *client_keeps says whether the client may keep its
+// window (gevws_deflate_negotiate_flags).
+std::string DeflateAnswer(const uint8_t* offer, uint64_t n, bool client_takeover = false,
+                          bool* client_keeps = nullptr);
 
 }  // namespace gevws

@@ -545,7 +545,8 @@ int gevws_messages_ext_async(gevws_ctx *ctx, void *stream,
  * fragments and the slots' padding are skipped, only hdr.length bytes of a
  * frame are read -- followed by the four bytes 00 00 ff ff (RFC 7692 section
  * 7.2.2).  No context takeover: every message starts with an empty window
- * (gevws_deflate_negotiate answers offers accordingly).
+ * (gevws_deflate_negotiate answers offers accordingly;
+ * gevws_inflate_ctx_async below is the step with client context takeover).
  *
  * Verdict.  S is raw DEFLATE (RFC 1951) read from bit 0.  A block that ends
  * with BFINAL set ends the message (the rest of S is ignored); a block that
@@ -597,6 +598,85 @@ int gevws_inflate_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_frame
  * NULL buffer; *out_len = the bytes written before the verdict. */
 int gevws_inflate_raw(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len);
 
+/* Client context takeover: the inflate step with a 32 KiB window per
+ * connection, kept between messages and between passes.  Additions to ABI
+ * version 3: nothing above changes.  (The outbound direction keeps
+ * server_no_context_takeover; a compressed message that spans two passes is
+ * still GEVWS_INF_PENDING.)
+ *
+ * GEVWS_EXT_CLIENT_TAKEOVER is a second bit of the d_conn_ext byte, set beside
+ * GEVWS_EXT_DEFLATE for a connection whose client may keep its LZ77 window
+ * (gevws_deflate_negotiate_flags says when).  The message pass looks at
+ * GEVWS_EXT_DEFLATE only: the byte 3 is the byte 1 to it.
+ *
+ * Semantics.  For such a connection let H be the last min(32 768, total) bytes
+ * of the inflated output of its earlier compressed messages -- earlier in this
+ * pass and in earlier passes, in stream order.  H is what zlib's window holds,
+ * so a distance of exactly 32 768 is allowed.  Verdict and bytes of the next
+ * compressed message with payload P are what the rules above give for the
+ * stream "H as stored blocks with BFINAL 0, then P" with max_message_bytes +
+ * |H| as the limit, the first |H| output bytes dropped: a distance may reach
+ * min(32 768, out + |H|) back, everything else is unchanged.
+ *   - A block with BFINAL set ends the message as above; the window continues.
+ *   - Uncompressed messages of the connection (RSV1 clear) do not enter the
+ *     window.
+ *   - A message that inflates but fails UTF-8 keeps the context: its bytes
+ *     are in the window.
+ *   - GEVWS_MSG_ERR_DEFLATE or GEVWS_MSG_ERR_TOO_BIG loses the context.  The
+ *     connection's later compressed messages in the batch get GEVWS_INF_DONE,
+ *     the first failure's status and length 0; they take no space and count
+ *     in `errors`.  The slot is marked broken and the mark is sticky: in later
+ *     passes every compressed message of the connection, whole or not, gets
+ *     that status without being decoded.  With d_state, `failed` is set as
+ *     above.
+ *   - A compressed message without BEGIN or END stops the connection's chain:
+ *     it and every later compressed message of the connection in the batch are
+ *     GEVWS_INF_PENDING, and the window stands where the last whole message
+ *     left it.  (A message without END is the connection's last; one without
+ *     BEGIN is its first, so the slot is left untouched.)  Shown again, whole,
+ *     in a later pass it is inflated then.
+ *   - GEVWS_ERR_CAPACITY: nothing is written and the slots are untouched, byte
+ *     for byte, so the retry sees the same contexts.
+ *
+ * The slot.  d_inf_ctx is a caller-owned device buffer of n_conns slots of
+ * GEVWS_INF_CTX_BYTES each, on a 16-byte boundary; connection c's is slot c.
+ * All-zero is a fresh connection.  Callers treat a slot as opaque; its layout
+ * is a 64-byte head -- uint64 total (little-endian: the bytes the connection's
+ * compressed messages have inflated to), uint8 broken (0, or the status that
+ * lost the context), zeros -- and behind it the ring image: stream byte i sits
+ * at ring[i & 32767], bytes never written stay zero.  A slot's content is a
+ * function of the connection's stream only, not of how the stream was cut
+ * into passes, and gevws_inflate_raw_ctx produces the same bytes on the host.
+ * 32 832 bytes a connection: 538 MB of device memory for 16 384 connections.
+ *
+ * gevws_inflate_ctx_async is gevws_inflate_async plus d_conn_ext (one byte per
+ * connection), d_inf_ctx and n_conns.  With either pointer NULL it is
+ * gevws_inflate_async bit for bit (which is that NULL call).  A connection
+ * without GEVWS_EXT_CLIENT_TAKEOVER is inflated as above and its slot is
+ * neither read nor written.  A takeover connection's messages depend on each
+ * other in order, so one wave inflates them one after another.  A message
+ * record with conn >= n_conns makes the call GEVWS_ERR_INVALID on the device:
+ * d_summary gets that status and the count of such records in `errors`, and
+ * nothing else is written (no slot is indexed by such a record).  With
+ * contexts max_messages is at most 0x7FF00000. */
+#define GEVWS_EXT_CLIENT_TAKEOVER 2u
+#define GEVWS_INF_CTX_BYTES (32768u + 64u)
+int gevws_inflate_ctx_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_frames, uint64_t max_frames,
+                            const gevws_message *d_messages, uint64_t max_messages, const int64_t *d_msg_of,
+                            const gevws_summary *d_msg_summary, const uint8_t *d_payload,
+                            uint64_t max_message_bytes, gevws_msg_state *d_state /* may be NULL */,
+                            gevws_inflated *d_inflated, uint8_t *d_out, uint64_t out_cap, gevws_summary *d_summary,
+                            const uint8_t *d_conn_ext, uint8_t *d_inf_ctx, uint32_t n_conns);
+
+/* gevws_inflate_raw over one slot in host memory (ctx[0, GEVWS_INF_CTX_BYTES)):
+ * the message is inflated with the slot's window behind it, and a message
+ * that inflates is appended to the window.  A failure marks the slot broken
+ * and leaves its window; a broken slot returns its status at once with
+ * *out_len = 0.  A zeroed slot gives gevws_inflate_raw's result.  A NULL ctx
+ * is GEVWS_ERR_INVALID. */
+int gevws_inflate_raw_ctx(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len,
+                          uint8_t *ctx);
+
 /* Answers a Sec-WebSocket-Extensions request value (offer[0, n)) for a server
  * that inflates on the device: the first permessage-deflate offer it can
  * serve is answered with
@@ -610,6 +690,20 @@ int gevws_inflate_raw(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap,
  * Returns GEVWS_OK, or GEVWS_ERR_CAPACITY when the answer does not fit
  * out[0, cap).  Meant to be called from the upgrader's extension_custom hook. */
 int gevws_deflate_negotiate(const uint8_t *offer, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len);
+
+/* The same with flags, and the byte to store in d_conn_ext for the connection
+ * (*conn_ext, may be NULL): GEVWS_EXT_DEFLATE, or 0 when no offer is usable.
+ * Flags 0 writes gevws_deflate_negotiate's answer byte for byte.
+ * GEVWS_NEGOTIATE_CLIENT_TAKEOVER leaves client_no_context_takeover out of the
+ * answer, and sets GEVWS_EXT_CLIENT_TAKEOVER in *conn_ext, unless the chosen
+ * offer carried the parameter: then it is echoed and the bit stays clear.
+ * server_no_context_takeover is always sent, server_max_window_bits echoed as
+ * above; client_max_window_bits is accepted and not echoed, so the client
+ * uses 15, which the 32 KiB window of gevws_inflate_ctx_async holds.  Any
+ * other flag bit is GEVWS_ERR_INVALID. */
+#define GEVWS_NEGOTIATE_CLIENT_TAKEOVER 1u
+int gevws_deflate_negotiate_flags(const uint8_t *offer, uint64_t n, uint32_t flags, uint8_t *out, uint64_t cap,
+                                  uint64_t *out_len, uint8_t *conn_ext);
 
 /* The deflate step: outbound messages compressed on the device, and the
  * gevws_out_frame records gevws_encode_batch_async frames them from.

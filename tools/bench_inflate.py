@@ -13,6 +13,15 @@ inflate step is timed by HIP events around its launches.  One JSON line per
 (shape, payload), medians over the rounds.
 
     python tools/bench_inflate.py [--rounds 7] [--warmup 2] [--shapes many,large]
+
+--takeover measures client context takeover instead (gevws_inflate_ctx_async):
+16 384 connections x 8 text messages of about 512 B, compressed by one
+persistent compressor per connection, against the same messages compressed
+independently -- the compressed bytes of both, the inflate step's time for
+both (alternating in one process), and zlib with a persistent decompressobj
+per connection.  Two JSON lines with "mode": "takeover".
+
+    python tools/bench_inflate.py --takeover [--commit ID]
 """
 from __future__ import annotations
 
@@ -97,6 +106,147 @@ def median(xs):
     return sorted(xs)[len(xs) // 2]
 
 
+TAKEOVER_CONNS, TAKEOVER_MSGS, TAKEOVER_BYTES, TAKEOVER_SCRIPTS = 16384, 8, 512, 64
+
+
+def inflate_chains(job):
+    """zlib over `count` connections cycling through `scripts` (a connection's
+    payloads in order): one persistent decompressobj a connection when `keep`,
+    a fresh one a message otherwise; (seconds, bytes out)."""
+    scripts, count, keep = job
+    t0 = time.perf_counter()
+    total = 0
+    for i in range(count):
+        d = zlib.decompressobj(-15)
+        for p in scripts[i % len(scripts)]:
+            if not keep:
+                d = zlib.decompressobj(-15)
+            total += len(d.decompress(p + TAIL))
+    return time.perf_counter() - t0, total
+
+
+def cpu_chain_baselines(scripts, n: int, keep: bool, rounds: int):
+    import multiprocessing as mp
+    one = sorted(inflate_chains((scripts, n, keep))[0] for _ in range(rounds))[rounds // 2]
+    jobs = [(scripts, n // 16 + (1 if k < n % 16 else 0), keep) for k in range(16)]
+    with mp.get_context("spawn").Pool(16) as pool:
+        pool.map(inflate_chains, jobs)
+        walls = []
+        for _ in range(rounds):
+            t0 = time.perf_counter()
+            pool.map(inflate_chains, jobs)
+            walls.append(time.perf_counter() - t0)
+    return one, sorted(walls)[rounds // 2]
+
+
+def takeover_main(args):
+    """--takeover: 16 384 connections x 8 text messages of about 512 B, each
+    connection's messages compressed by one persistent compressor (client
+    context takeover) against the same messages compressed independently; the
+    inflate step of both, alternating in one process."""
+    import numpy as np
+    rng = np.random.default_rng(0x74616B)
+    n, per = TAKEOVER_CONNS, TAKEOVER_MSGS
+    texts = [[text(TAKEOVER_BYTES - 32 + int(rng.integers(0, 64)), rng) for _ in range(per)]
+             for _ in range(TAKEOVER_SCRIPTS)]
+    kept, alone = [], []
+    for script in texts:
+        c = zlib.compressobj(6, zlib.DEFLATED, -15)
+        kept.append([(c.compress(t) + c.flush(zlib.Z_SYNC_FLUSH))[:-4] for t in script])
+        alone.append([deflate(t, 6) for t in script])
+    cpu = {}
+    if not args.no_cpu:
+        cpu = {"takeover": cpu_chain_baselines(kept, n, True, args.rounds),
+               "independent": cpu_chain_baselines(alone, n, False, args.rounds)}
+
+    import torch
+
+    import gev_amd
+
+    dev = torch.device("cuda", 0)
+    eng = gev_amd.Engine(0)
+    nm = n * per
+    inflated_bytes = sum(len(t) for i in range(n) for t in texts[i % TAKEOVER_SCRIPTS])
+    limit = max(len(t) for s in texts for t in s)
+    ctx = torch.zeros((n, gev_amd.INF_CTX_BYTES), dtype=torch.uint8, device=dev)
+    runs = {}
+    for mode, scripts, ext_byte in (("takeover", kept, 3), ("independent", alone, 1)):
+        streams = [np.concatenate([wire_frame(p, bytes(rng.integers(1, 256, 4).astype("u1"))) for p in s])
+                   for s in scripts]
+        lens = np.array([streams[i % TAKEOVER_SCRIPTS].size for i in range(n)], np.int64)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]])
+        in_bytes = int(lens.sum())
+        arena = torch.zeros(in_bytes + gev_amd.IN_PAD, dtype=torch.uint8, device=dev)
+        arena[:in_bytes] = torch.from_numpy(np.concatenate([streams[i % TAKEOVER_SCRIPTS] for i in range(n)])).to(dev)
+        comp_bytes = sum(len(p) for i in range(n) for p in scripts[i % TAKEOVER_SCRIPTS])
+        payload_cap = sum((len(p) + 15) // 16 * 16 for i in range(n) for p in scripts[i % TAKEOVER_SCRIPTS])
+        runs[mode] = dict(
+            arena=arena, in_bytes=in_bytes, conns=torch.from_numpy(np.stack([offs, lens], 1)).to(dev),
+            comp_bytes=comp_bytes, payload_cap=payload_cap, out=eng.alloc_batch(n, nm, payload_cap),
+            ext=torch.full((n,), ext_byte, dtype=torch.uint8, device=dev), t_inf=[], t_msg=[])
+    msgs = torch.empty((nm, 32), dtype=torch.uint8, device=dev)
+    msg_of = torch.empty(nm, dtype=torch.int64, device=dev)
+    conn_msg = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    msum = torch.zeros(64, dtype=torch.uint8, device=dev)
+    inflated = torch.empty((nm, 32), dtype=torch.uint8, device=dev)
+    out_cap = nm * ((limit + 15) // 16 * 16)
+    d_out = torch.empty(out_cap, dtype=torch.uint8, device=dev)
+    isum = torch.zeros(64, dtype=torch.uint8, device=dev)
+
+    def one_round(r, timed):
+        ctx.zero_()  # fresh connections (outside the timed span)
+        eng.decode_async(r["arena"], r["in_bytes"], r["conns"], n, r["out"], nm, r["payload_cap"])
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        eng.messages_ext_async(r["out"].frames, nm, r["out"].conn_out, n, r["out"].summary, r["out"].payload, None,
+                               msgs, nm, msg_of, conn_msg, msum, r["ext"])
+        e[1].record()
+        if r is runs["takeover"]:
+            eng.inflate_ctx_async(r["out"].frames, nm, msgs, nm, msg_of, msum, r["out"].payload, limit, None,
+                                  inflated, d_out, out_cap, isum, r["ext"], ctx, n)
+        else:  # today's call
+            eng.inflate_async(r["out"].frames, nm, msgs, nm, msg_of, msum, r["out"].payload, limit, None, inflated,
+                              d_out, out_cap, isum)
+        e[2].record()
+        torch.cuda.synchronize()
+        if timed:
+            r["t_msg"].append(e[0].elapsed_time(e[1]))
+            r["t_inf"].append(e[1].elapsed_time(e[2]))
+
+    for mode, r in runs.items():  # warm-up, and the bytes are the texts
+        for _ in range(args.warmup):
+            one_round(r, False)
+        s = isum.cpu().numpy().view(gev_amd.SUMMARY_DTYPE)[0]
+        assert (int(s["status"]), int(s["frames"]), int(s["errors"]), int(s["payload_len"])) == \
+            (0, nm, 0, inflated_bytes), (mode, s)
+        rec = inflated.cpu().numpy().reshape(-1).view(gev_amd.INFLATED_DTYPE)
+        for i in (0, 1, per - 1, per, nm - 1):
+            o, want = int(rec["out_off"][i]), texts[(i // per) % TAKEOVER_SCRIPTS][i % per]
+            assert d_out[o:o + len(want)].cpu().numpy().tobytes() == want, (mode, i)
+    for _ in range(args.rounds):  # the two alternate
+        for r in runs.values():
+            one_round(r, True)
+    for mode, r in runs.items():
+        m = median(r["t_inf"])
+        line = {"path": "inflate step, client context takeover (one wave per connection's chain) against the same "
+                        "messages compressed independently (one wave per message)",
+                "mode": "takeover", "variant": mode, "commit": args.commit, "connections": n,
+                "messages_per_connection": per, "messages": nm, "inflated_bytes": inflated_bytes,
+                "compressed_bytes": r["comp_bytes"],
+                "compressed_vs_independent": round(r["comp_bytes"] / runs["independent"]["comp_bytes"], 4),
+                "inflate_ms": round(m, 4), "inflate_rounds_ms": [round(t, 4) for t in r["t_inf"]],
+                "inflate_out_GBps": round(inflated_bytes / m / 1e6, 2), "messages_ms": round(median(r["t_msg"]), 4),
+                "context_bytes": n * gev_amd.INF_CTX_BYTES if mode == "takeover" else 0,
+                "rounds": args.rounds, "warmup": args.warmup}
+        if mode in cpu:
+            one, many = cpu[mode]
+            line.update({"zlib_1core_ms": round(one * 1e3, 2), "zlib_16proc_ms": round(many * 1e3, 2),
+                         "zlib_1core_out_GBps": round(inflated_bytes / one / 1e9, 3),
+                         "zlib_16proc_out_GBps": round(inflated_bytes / many / 1e9, 3)})
+        print(json.dumps(line), flush=True)
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -104,7 +254,12 @@ def main():
     ap.add_argument("--shapes", default="many,large")
     ap.add_argument("--kinds", default="text,stored")
     ap.add_argument("--no-cpu", action="store_true", help="skip the zlib baselines")
+    ap.add_argument("--takeover", action="store_true",
+                    help="client context takeover against independently compressed messages (16 384 x 8 x ~512 B)")
+    ap.add_argument("--commit", default="", help="recorded in the --takeover lines")
     args = ap.parse_args()
+    if args.takeover:
+        return takeover_main(args)
     import numpy as np
 
     rng = np.random.default_rng(0x696E66)
