@@ -28,6 +28,7 @@ from ._abi import (MSG_BEGIN, MSG_END, MSG_ERR_CONTINUATION, MSG_ERR_CONTROL, MS
 from ._abi import EXT_DEFLATE, INF_DONE, INF_PENDING, MSG_COMPRESSED, MSG_ERR_DEFLATE, MSG_ERR_TOO_BIG
 from ._abi import EXT_CLIENT_TAKEOVER, INF_CTX_BYTES, NEGOTIATE_CLIENT_TAKEOVER
 from ._abi import DEFLATE_DYNAMIC, DEFLATE_PLAIN_IF_NOT_SMALLER
+from ._abi import DEF_CTX_BYTES, EXT_SERVER_TAKEOVER, NEGOTIATE_SERVER_TAKEOVER
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
                    SUMMARY_UNORDERED, TILE, Header)
@@ -140,6 +141,41 @@ def deflate_raw(b: bytes, window_bits: int = 0, flags: int = 0) -> bytes:
     if st != OK:
         raise RuntimeError(f"gevws_deflate_raw_flags: {status_string(st)}")
     return out.raw[: n.value]
+
+
+def deflate_raw_ctx(b: bytes, ctx: bytearray, window_bits: int = 0, flags: int = 0) -> bytes:
+    """gevws_deflate_raw_ctx: deflate_raw over one connection's context slot (a
+    bytearray of DEF_CTX_BYTES, zeroed for a fresh connection, updated in
+    place): the message is compressed with the connection's earlier messages
+    as history and appended to the slot -- the payload gevws_deflate_ctx_async
+    writes for it, byte for byte."""
+    b = bytes(b)
+    if not isinstance(ctx, bytearray) or len(ctx) != DEF_CTX_BYTES:
+        raise ValueError("ctx: a bytearray of DEF_CTX_BYTES")
+    cap = deflate_bound(len(b))
+    out = ctypes.create_string_buffer(cap)
+    n = ctypes.c_uint64(0)
+    slot = (ctypes.c_uint8 * DEF_CTX_BYTES).from_buffer(ctx)
+    st = lib.gevws_deflate_raw_ctx(ctypes.c_char_p(b), len(b), window_bits, flags, out, cap, ctypes.byref(n), slot)
+    if st != OK:
+        raise RuntimeError(f"gevws_deflate_raw_ctx: {status_string(st)}")
+    return out.raw[: n.value]
+
+
+def deflate_negotiate_takeover(value: bytes, flags: int = 0) -> Tuple[bytes, int]:
+    """gevws_deflate_negotiate_takeover: (the answer, the connection's conn_ext
+    byte).  NEGOTIATE_CLIENT_TAKEOVER as in deflate_negotiate_ext; with
+    NEGOTIATE_SERVER_TAKEOVER the server may keep its window unless the offer
+    said otherwise: the byte then carries EXT_SERVER_TAKEOVER."""
+    value = bytes(value)
+    out = ctypes.create_string_buffer(256)
+    n = ctypes.c_uint64(0)
+    ext = ctypes.c_uint8(0)
+    st = lib.gevws_deflate_negotiate_takeover(ctypes.c_char_p(value), len(value), flags, out, len(out),
+                                              ctypes.byref(n), ctypes.byref(ext))
+    if st != OK:
+        raise RuntimeError(f"gevws_deflate_negotiate_takeover: {status_string(st)}")
+    return out.raw[: n.value], int(ext.value)
 
 
 def deflate_negotiate(value: bytes) -> bytes:
@@ -667,25 +703,55 @@ class Engine:
         if st != OK:
             raise RuntimeError(f"gevws_deflate_async: {status_string(st)}")
 
+    def deflate_ctx_async(self, msgs, max_msgs: int, prev, src, src_bytes: int, flags: int, out_frames, out,
+                          out_cap: int, summary, msg_conn, conn_ext, contexts, n_conns: int, stream=None) -> None:
+        """gevws_deflate_ctx_async: deflate_async with server context takeover
+        -- msg_conn: uint32 [max_msgs] (each message's connection), conn_ext:
+        uint8 [n_conns] (EXT_DEFLATE | EXT_SERVER_TAKEOVER), contexts: uint8
+        [n_conns, DEF_CTX_BYTES], zeroed for fresh connections and carried from
+        call to call.  Any of the three None is deflate_async."""
+        st = lib.gevws_deflate_ctx_async(
+            self._ctx, _stream_handle(stream), msgs.data_ptr() if max_msgs else None, max_msgs,
+            prev.data_ptr() if prev is not None else None, src.data_ptr() if max_msgs else None, src_bytes, flags,
+            out_frames.data_ptr() if max_msgs else None, out.data_ptr() if max_msgs else None, out_cap,
+            summary.data_ptr(), msg_conn.data_ptr() if msg_conn is not None else None,
+            conn_ext.data_ptr() if conn_ext is not None else None,
+            contexts.data_ptr() if contexts is not None else None, n_conns)
+        if st != OK:
+            raise RuntimeError(f"gevws_deflate_ctx_async: {status_string(st)}")
+
     def deflate(self, msgs: np.ndarray, src, src_bytes: int, flags: int = 0, out_cap: Optional[int] = None,
-                stream=None) -> "Deflated":
+                stream=None, msg_conn=None, conn_ext=None, contexts=None) -> "Deflated":
         """The deflate step over host records (DEFLATE_MSG_DTYPE) whose bytes
         live in the device tensor `src` (src_bytes + IN_PAD long).  Grows the
         output once on ERR_CAPACITY (nothing is written by the call that did
-        not fit)."""
+        not fit).  With msg_conn (uint32 [n], host or device), conn_ext and
+        contexts (uint8 [n_conns, DEF_CTX_BYTES], the caller's, carried from
+        call to call) connections with EXT_SERVER_TAKEOVER keep their window
+        between messages; the call that did not fit leaves the contexts
+        untouched too."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n = int(msgs.shape[0])
         d_msgs = torch.from_numpy(np.ascontiguousarray(msgs).view(np.uint8).reshape(-1, 24).copy()).to(dev) \
             if n else torch.zeros((1, 24), dtype=torch.uint8, device=dev)
+        with_ctx = msg_conn is not None and conn_ext is not None and contexts is not None
+        d_conn = None
+        if with_ctx:
+            d_conn = msg_conn if hasattr(msg_conn, "data_ptr") else \
+                torch.from_numpy(np.ascontiguousarray(msg_conn, dtype=np.uint32).view(np.int32).copy()).to(dev)
         if out_cap is None:  # text compresses several-fold; the retry covers what does not
             out_cap = int(msgs["length"].sum()) // 2 + 16 * n
         for attempt in range(2):
             res = Deflated(frames=torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=dev),
                            out=torch.empty(out_cap + _abi.OUT_PAD, dtype=torch.uint8, device=dev),
                            summary=torch.zeros(64, dtype=torch.uint8, device=dev), n_messages=n)
-            self.deflate_async(d_msgs, n, None, src, src_bytes, flags, res.frames, res.out, out_cap, res.summary,
-                               stream)
+            if with_ctx:
+                self.deflate_ctx_async(d_msgs, n, None, src, src_bytes, flags, res.frames, res.out, out_cap,
+                                       res.summary, d_conn, conn_ext, contexts, int(contexts.shape[0]), stream)
+            else:
+                self.deflate_async(d_msgs, n, None, src, src_bytes, flags, res.frames, res.out, out_cap, res.summary,
+                                   stream)
             torch.cuda.synchronize(self.device)
             s = res.summary_host()
             if int(s["status"]) == ERR_CAPACITY and attempt == 0:
@@ -1334,4 +1400,6 @@ __all__ = ["Engine", "Batch", "Comm", "RingBuffer", "Connection", "Protocol", "H
            "status_string", "device_count", "lib", "FRAME_DTYPE", "CONN_OUT_DTYPE", "SUMMARY_DTYPE",
            "SYNTH_DTYPE", "OUT_FRAME_DTYPE", "OK", "NEED_MORE", "ERR_LEN_MSB", "ERR_CAPACITY", "ERR_INVALID", "ERR_DEVICE",
            "ERR_NOT_UPGRADED", "IN_PAD", "PAYLOAD_ALIGN", "TILE", "SUMMARY_UNORDERED",
-           "DEFLATE_MSG_DTYPE", "DEFLATE_PLAIN_IF_NOT_SMALLER", "DEFLATE_DYNAMIC", "Deflated", "deflate_raw", "deflate_bound"]
+           "DEFLATE_MSG_DTYPE", "DEFLATE_PLAIN_IF_NOT_SMALLER", "DEFLATE_DYNAMIC", "Deflated", "deflate_raw", "deflate_bound",
+           "deflate_raw_ctx", "deflate_negotiate_takeover", "DEF_CTX_BYTES", "EXT_SERVER_TAKEOVER",
+           "NEGOTIATE_SERVER_TAKEOVER"]

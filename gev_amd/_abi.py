@@ -73,6 +73,9 @@ EXT_DEFLATE = 1
 EXT_CLIENT_TAKEOVER = 2  # conn_ext bit: the client keeps its window (gevws_inflate_ctx_async)
 INF_CTX_BYTES = 32768 + 64  # one connection's slot of d_inf_ctx
 NEGOTIATE_CLIENT_TAKEOVER = 1  # gevws_deflate_negotiate_flags flag
+EXT_SERVER_TAKEOVER = 4  # conn_ext bit: the server keeps its window (gevws_deflate_ctx_async)
+DEF_CTX_BYTES = 64 + 32768 + 8192  # one connection's slot of d_def_ctx
+NEGOTIATE_SERVER_TAKEOVER = 2  # gevws_deflate_negotiate_takeover flag
 INF_DONE = 1
 INF_PENDING = 2
 
@@ -285,6 +288,12 @@ SIGNATURES = {
                                          ctypes.POINTER(ctypes.c_uint64)]),
     "gevws_deflate_raw_flags": (ctypes.c_int, [P, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, P, ctypes.c_uint64,
                                                ctypes.POINTER(ctypes.c_uint64)]),
+    "gevws_deflate_ctx_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, ctypes.c_uint64, ctypes.c_uint32, P, P,
+                                               ctypes.c_uint64, P, P, P, P, ctypes.c_uint32]),
+    "gevws_deflate_raw_ctx": (ctypes.c_int, [P, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, P, ctypes.c_uint64,
+                                             ctypes.POINTER(ctypes.c_uint64), P]),
+    "gevws_deflate_negotiate_takeover": (ctypes.c_int, [P, ctypes.c_uint64, ctypes.c_uint32, P, ctypes.c_uint64,
+                                                        ctypes.POINTER(ctypes.c_uint64), P]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),
     "gevws_synth_async": (ctypes.c_int, [P, P, P, P, ctypes.c_uint64, ctypes.c_uint64]),
     "gevws_synth_verify_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P,

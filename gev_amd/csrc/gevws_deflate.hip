@@ -29,6 +29,16 @@
 // With GEVWS_DEFLATE_DYNAMIC the two kernels run as k_def_size<true> /
 // k_def_emit<true>: a run may become a dynamic-Huffman block (DefWaveDyn
 // below).  46 032 B of LDS when sizing, 53 496 B when emitting: 3 waves a CU.
+//
+// gevws_deflate_ctx_async (server context takeover) launches the <DYN, true>
+// instances, which serve both kinds of connection with a wave-uniform branch:
+// a connection without the takeover bit runs the code above; a takeover
+// connection's messages are a chain that the wave of the run's first message
+// compresses in order, in both passes, the window and the hash table carried
+// in the connection's slot of d_def_ctx (see "context takeover" below).  The
+// slot's ring and table ARE the LDS window and table, so the <DYN, true>
+// instances hold the LDS of their twins.  The <DYN, false> instances are the
+// kernels of gevws_deflate_async, unchanged.
 #include "gevws_deflate_core.hpp"
 #include "gevws_internal.hpp"
 
@@ -59,21 +69,23 @@ struct DefRec {  // per message, between the passes
 struct DefScratch {
   uint64_t* blk;  // per message: [1, bytes of d_out, wire length, 1 if malformed]
   DefRec* rec;
+  uint32_t* heads;  // with contexts, per connection: the runs of a takeover connection in the list
   size_t total;
 };
-inline DefScratch def_scratch(void* base, uint64_t max_msgs) {
+inline DefScratch def_scratch(void* base, uint64_t max_msgs, uint32_t n_conns = 0) {
   auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
   uint8_t* p = static_cast<uint8_t*>(base);
   DefScratch s;
   size_t o = 0;
   s.blk = reinterpret_cast<uint64_t*>(p + o), o += up(max_msgs * kBlkFields * sizeof(uint64_t));
   s.rec = reinterpret_cast<DefRec*>(p + o), o += up(max_msgs * sizeof(DefRec));
+  s.heads = reinterpret_cast<uint32_t*>(p + o), o += up((size_t)n_conns * sizeof(uint32_t));
   s.total = o;
   return s;
 }
 
-// 4 input bytes at any position of the window (byte i of the message is at
-// ring byte i mod 32 768).
+// 4 input bytes at any position of the window (stream byte i -- byte i of the
+// message without a context -- is at ring byte i mod 32 768).
 struct DefReader {
   const uint32_t* ring;
   __device__ __forceinline__ uint32_t u32(uint64_t pos) const {
@@ -91,7 +103,17 @@ struct DefReader {
   }
 };
 
-template <bool EMIT>
+// Bytes [lo, hi) of a vector (0 <= lo, hi <= 16).
+__device__ __forceinline__ u32x4 byte_range16(int64_t lo, int64_t hi) {
+  const u32x4 ones{~0u, ~0u, ~0u, ~0u};
+  const u32x4 a = keep_bytes(ones, hi), b = keep_bytes(ones, lo);
+  return u32x4{a[0] & ~b[0], a[1] & ~b[1], a[2] & ~b[2], a[3] & ~b[3]};
+}
+
+// CTX: a message of a context-takeover chain.  The ring and the table are the
+// connection's, the message starts at stream position `base`, which is not
+// 16-aligned in general, and every position is a stream position.
+template <bool EMIT, bool CTX = false>
 struct DefWave {
   DefReader rd;
   uint32_t* ring;
@@ -100,26 +122,66 @@ struct DefWave {
   const uint8_t* src;         // the message's bytes (16-byte aligned)
   uint8_t* out;               // EMIT: its payload in d_out (16-byte aligned)
   uint64_t slot;              // EMIT: the bytes of d_out it owns
-  uint64_t hi = 0;            // input bytes staged (whole KiB)
+  uint64_t hi = 0;            // input bytes staged (whole KiB; CTX: the stream position staged up to)
+  uint64_t base = 0;          // CTX: the message's first byte in the stream
   uint64_t flushed = 0;       // payload bytes in d_out (whole vectors)
   uint32_t lane;
   uint32_t len = 0, dist = 0, byte = 0;  // the lane's position in this step
   uint32_t carry = 0;         // lanes 0..3: the staging buffer's first words at the run's start
 
   __device__ DefWave(uint32_t* ring_, uint16_t* tab_, uint32_t* obuf_, const uint8_t* src_, uint8_t* out_,
-                     uint64_t slot_)
-      : rd{ring_}, ring(ring_), tab(tab_), obuf(obuf_), src(src_), out(out_), slot(slot_), lane(threadIdx.x & 63) {}
+                     uint64_t slot_, uint64_t base_ = 0)
+      : rd{ring_}, ring(ring_), tab(tab_), obuf(obuf_), src(src_), out(out_), slot(slot_), lane(threadIdx.x & 63) {
+    if constexpr (CTX) base = base_, hi = base_ & ~15ull;
+  }
 
   // The next KiB of the message into the window while the step's reach
   // (p0 + 64 + 258 + 8) may pass what is there.  At most 2 KiB are ever ahead
   // of p0, so the 30 KiB behind every position of the step stay.
+  //
+  // CTX: the ring vectors are the stream's, so the message's bytes are shifted
+  // into them from two aligned source vectors (never one before the message's
+  // first or wholly behind its last byte), and the vectors that hold its first
+  // and its last byte are merged: the bytes before the message are the nearest
+  // history, the bytes behind it the oldest -- or, while the stream is shorter
+  // than the ring, zeros -- whatever lies behind the message in d_src.
   __device__ __forceinline__ void stage(uint64_t p0, uint64_t n) {
-    while (hi < n && hi < p0 + kStage) {
-      const uint64_t o = hi + 16 * lane;
-      if (o < n)
-        *reinterpret_cast<u32x4*>(ring + (((uint32_t)o & (kWin - 1)) >> 2)) = *reinterpret_cast<const u32x4*>(src + o);
-      wave_lds_order();
-      hi += kStage;
+    if constexpr (CTX) {
+      const uint32_t s = (uint32_t)base & 15;
+      const uint64_t len = n - base;  // (n: the message's end in the stream)
+      while (hi < n && hi < p0 + kStage) {
+        const uint64_t x = hi + 16 * lane;  // a whole vector of the stream
+        if (x < n) {
+          const uint64_t j = (x + s - base) >> 4;  // source vector j holds message bytes [16 j, 16 j + 16)
+          const u32x4 zero{0, 0, 0, 0};
+          const u32x4 b = 16 * j < len ? *reinterpret_cast<const u32x4*>(src + 16 * j) : zero;
+          u32x4 v = b;
+          if (s) {
+            const u32x4 a = j ? *reinterpret_cast<const u32x4*>(src + 16 * (j - 1)) : zero;
+            v = funnel16(a, b, 16 - s);
+          }
+          u32x4* at = reinterpret_cast<u32x4*>(ring + (((uint32_t)x & (kWin - 1)) >> 2));
+          const int64_t lo = x < base ? (int64_t)(base - x) : 0, hi16 = n - x < 16 ? (int64_t)(n - x) : 16;
+          if (lo > 0 || hi16 < 16) {
+            u32x4 old = *at;
+            if (x < kWin) old = keep_bytes(old, lo);  // nothing was ever written behind the message
+            const u32x4 m = byte_range16(lo, hi16);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = (v[i] & m[i]) | (old[i] & ~m[i]);
+          }
+          *at = v;
+        }
+        wave_lds_order();
+        hi += kStage;
+      }
+    } else {
+      while (hi < n && hi < p0 + kStage) {
+        const uint64_t o = hi + 16 * lane;
+        if (o < n)
+          *reinterpret_cast<u32x4*>(ring + (((uint32_t)o & (kWin - 1)) >> 2)) = *reinterpret_cast<const u32x4*>(src + o);
+        wave_lds_order();
+        hi += kStage;
+      }
     }
   }
 
@@ -205,11 +267,11 @@ struct DefWave {
     if (lane == 0) or_bits(bit, v);
     wave_lds_order();
   }
-  // A run starts on a 4 KiB boundary: whole words of the window.
+  // A run starts on a 4 KiB boundary: whole words of the window.  (CTX: anywhere.)
   __device__ __forceinline__ void stored(uint64_t from, uint32_t n, uint64_t byte_at) {
     const uint32_t nw = (n + 3) >> 2, w0 = (uint32_t)from >> 2;
     for (uint32_t i = lane; i < nw; i += kDefBlock) {
-      uint32_t v = ring[(w0 + i) & (kRingWords - 1)];
+      uint32_t v = CTX ? rd.u32(from + 4 * (uint64_t)i) : ring[(w0 + i) & (kRingWords - 1)];
       const uint32_t rem = n - 4 * i;
       if (rem < 4) v &= (1u << (8 * rem)) - 1u;
       or_bits(8 * (byte_at + 4 * (uint64_t)i), v);
@@ -249,9 +311,9 @@ constexpr uint32_t kScrAt = kOutWords - kScrWords;  // (when emitting)
 static_assert(kScrWords <= kOutWords && kScrAt % 4 == 0 && kScrAt * 32 >= 128 + 3 + kMaxHeaderBits + 64,
               "the dynamic header ends below the scratch in the staging buffer");
 
-template <bool EMIT>
-struct DefWaveDyn : DefWave<EMIT> {
-  using B = DefWave<EMIT>;
+template <bool EMIT, bool CTX = false>
+struct DefWaveDyn : DefWave<EMIT, CTX> {
+  using B = DefWave<EMIT, CTX>;
   uint32_t* T;       // kTab
   uint32_t* scr;     // kScrWords
   uint64_t* lm;      // EMIT: kMaskWords, the literal positions of the run
@@ -260,8 +322,9 @@ struct DefWaveDyn : DefWave<EMIT> {
   uint32_t nmatch = 0;
 
   __device__ DefWaveDyn(uint32_t* ring_, uint16_t* tab_, uint32_t* obuf_, const uint8_t* src_, uint8_t* out_,
-                        uint64_t slot_, uint32_t* T_, uint32_t* scr_, uint64_t* lm_, uint64_t* tm_, uint32_t* match_)
-      : B(ring_, tab_, obuf_, src_, out_, slot_), T(T_), scr(scr_), lm(lm_), tm(tm_), match(match_) {}
+                        uint64_t slot_, uint32_t* T_, uint32_t* scr_, uint64_t* lm_, uint64_t* tm_, uint32_t* match_,
+                        uint64_t base_ = 0)
+      : B(ring_, tab_, obuf_, src_, out_, slot_, base_), T(T_), scr(scr_), lm(lm_), tm(tm_), match(match_) {}
 
   __device__ __forceinline__ uint32_t* table() { return T; }
   __device__ __forceinline__ uint32_t* scratch() { return scr; }
@@ -378,47 +441,146 @@ struct DefWaveDyn : DefWave<EMIT> {
   }
 };
 
+// ------------------------------------------------------------------ context takeover
+// A takeover connection's messages depend on each other in order (message k's
+// window is the messages before it), so the wave of the run's first message
+// walks the run, one message after another, and the waves of its other
+// messages exit -- in both passes, because the sizing needs the matches and so
+// the window too.  Both passes load the slot (include/gevws.h: a 64-byte head,
+// the ring image, the hash table) into the LDS ring and table at its own
+// indices and carry the stream position in registers; the sizing pass writes
+// nothing to the slot, the emit pass stores what it produced at the chain's end.
+constexpr uint32_t kCtxHead = 64;
+static_assert(GEVWS_DEF_CTX_BYTES == kCtxHead + kWin + 2 * kHashSlots && GEVWS_DEF_CTX_BYTES % 16 == 0,
+              "slots, their rings and their tables lie on 16-byte boundaries");
+
+// The message of a workgroup: with contexts the grid is kDefSpread x q
+// workgroups and workgroup b takes message (b % kDefSpread) q + b / kDefSpread,
+// the inflate step's mapping (gevws_inflate.hip): a chain's
+// work sits in its first message's workgroup, and with a regular number of
+// messages a connection the identity would put every chain head on one XCD.
+constexpr uint32_t kDefSpread = 1024;
+inline uint32_t def_grid_q(uint32_t nm) {
+  const uint32_t q = (nm + kDefSpread - 1) / kDefSpread;
+  return q <= 8 ? q : (q + 15) / 16 * 16;
+}
+template <bool CTX>
+__device__ __forceinline__ uint64_t def_block_message() {
+  if constexpr (CTX) return (uint64_t)(blockIdx.x % kDefSpread) * (gridDim.x / kDefSpread) + blockIdx.x / kDefSpread;
+  else return blockIdx.x;
+}
+
+// The slot's valid part into the LDS ring and table; the connection's stream position.
+__device__ __forceinline__ uint64_t def_load_slot(const uint8_t* __restrict__ slot, uint32_t* s_ring, uint16_t* s_tab) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t total = uniform64(*reinterpret_cast<const uint64_t*>(slot));
+  const uint32_t valid = total < kWin ? (uint32_t)round16(total) : kWin;
+  for (uint32_t o = 16 * lane; o < valid; o += 16 * kDefBlock)
+    *reinterpret_cast<u32x4*>(s_ring + (o >> 2)) = *reinterpret_cast<const u32x4*>(slot + kCtxHead + o);
+  for (uint32_t j = lane; j < kHashSlots / 8; j += kDefBlock)
+    reinterpret_cast<u32x4*>(s_tab)[j] = reinterpret_cast<const u32x4*>(slot + kCtxHead + kWin)[j];
+  wave_lds_order();
+  return total;
+}
+
 // ------------------------------------------------------------------ 1. checks and sizes
-template <bool DYN>
+// Message k: its record checked, its payload sized.  CHAIN: it continues a
+// takeover connection's stream at `total` (the LDS ring and table are the
+// connection's); returns the stream position behind it.
+template <bool DYN, bool CHAIN>
+__device__ __forceinline__ uint64_t def_size_one(uint64_t k, const gevws_deflate_msg* __restrict__ msgs,
+                                                 const uint8_t* __restrict__ src, uint64_t src_bytes, uint32_t flags,
+                                                 uint64_t* __restrict__ blk, DefRec* __restrict__ rec,
+                                                 uint32_t* s_ring, uint16_t* s_tab, uint32_t* s_T, uint32_t* s_scr,
+                                                 uint64_t total, bool& bad) {
+  const gevws_deflate_msg msg = msgs[k];
+  const uint64_t off = uniform64(msg.payload_off), n = uniform64(msg.length);
+  const uint32_t wb = uniform32(msg.window_bits), op = uniform32(msg.opcode);
+  // (`bad` is handed out although no caller reads it: with it the <DYN, false>
+  // kernels keep the instructions they had before there were contexts, and one
+  // more scalar instruction in this prologue measured 0.5 % -- DESIGN section 5.7)
+  bad = (op != 1 && op != 2) || (wb != 0 && (wb < 8 || wb > 15)) || (off & (GEVWS_PAYLOAD_ALIGN - 1)) ||
+        n > 0xFFFFFFFFull || n > src_bytes || off > src_bytes - n;
+  if (bad) {  // (the call is GEVWS_ERR_INVALID; a chain goes on without the message)
+    if (threadIdx.x == 0) blk[k * kBlkFields + 3] = 1;
+    return total;
+  }
+  if constexpr (!CHAIN) {
+    for (uint32_t j = threadIdx.x; j < kHashSlots / 8; j += kDefBlock)
+      reinterpret_cast<u32x4*>(s_tab)[j] = u32x4{0, 0, 0, 0};
+    wave_lds_order();
+  }
+  uint64_t c;
+  if constexpr (DYN) {
+    DefWaveDyn<false, CHAIN> w(s_ring, s_tab, nullptr, src + off, nullptr, 0, s_T, s_scr, nullptr, nullptr, nullptr,
+                               total);
+    c = deflate_dyn<false>(w, n, max_dist(wb), total);
+  } else {
+    DefWave<false, CHAIN> w(s_ring, s_tab, nullptr, src + off, nullptr, 0, total);
+    c = deflate<false>(w, n, max_dist(wb), total);
+  }
+  // (a takeover connection's message is never sent plain: it would have to stay out of the peer's window)
+  const bool plain = !CHAIN && (flags & GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER) && c >= n;
+  const uint64_t wire = plain ? n : c;
+  if (threadIdx.x == 0) {
+    rec[k] = DefRec{(uint32_t)wire, plain ? 1u : 0u};
+    blk[k * kBlkFields + 0] = 1;
+    blk[k * kBlkFields + 1] = round16(wire);
+    blk[k * kBlkFields + 2] = wire;
+  }
+  return total + n;
+}
+
+// CTX: contexts are given (gevws_deflate_ctx_async); <DYN, false> is the kernel
+// of gevws_deflate_async.
+template <bool DYN, bool CTX>
 __global__ __launch_bounds__(kDefBlock) void k_def_size(const gevws_deflate_msg* __restrict__ msgs, uint64_t max_msgs,
                                                         const gevws_summary* __restrict__ gate,
                                                         const uint8_t* __restrict__ src, uint64_t src_bytes,
                                                         uint32_t flags, uint64_t* __restrict__ blk,
-                                                        DefRec* __restrict__ rec) {
+                                                        DefRec* __restrict__ rec,
+                                                        const uint32_t* __restrict__ msg_conn,
+                                                        const uint8_t* __restrict__ conn_ext,
+                                                        const uint8_t* __restrict__ def_ctx, uint32_t n_conns,
+                                                        uint32_t* __restrict__ heads) {
   __shared__ __attribute__((aligned(16))) uint32_t s_ring[kRingWords];
   __shared__ __attribute__((aligned(16))) uint16_t s_tab[kHashSlots];
-  const uint64_t m = blockIdx.x;
-  if (m >= gated_count(max_msgs, gate)) return;  // (blk and rec are zeroed)
-  const gevws_deflate_msg msg = msgs[m];
-  const uint64_t off = uniform64(msg.payload_off), n = uniform64(msg.length);
-  const uint32_t wb = uniform32(msg.window_bits), op = uniform32(msg.opcode);
-  const bool bad = (op != 1 && op != 2) || (wb != 0 && (wb < 8 || wb > 15)) || (off & (GEVWS_PAYLOAD_ALIGN - 1)) ||
-                   n > 0xFFFFFFFFull || n > src_bytes || off > src_bytes - n;
-  if (bad) {
-    if (threadIdx.x == 0) blk[m * kBlkFields + 3] = 1;
-    return;
-  }
-  for (uint32_t j = threadIdx.x; j < kHashSlots / 8; j += kDefBlock)
-    reinterpret_cast<u32x4*>(s_tab)[j] = u32x4{0, 0, 0, 0};
-  wave_lds_order();
-  uint64_t c;
+  uint32_t *s_T = nullptr, *s_scr = nullptr;
   if constexpr (DYN) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_T[kTab];
-    __shared__ __attribute__((aligned(16))) uint32_t s_scr[kScrWords];
-    DefWaveDyn<false> w(s_ring, s_tab, nullptr, src + off, nullptr, 0, s_T, s_scr, nullptr, nullptr, nullptr);
-    c = deflate_dyn<false>(w, n, max_dist(wb));
-  } else {
-    DefWave<false> w(s_ring, s_tab, nullptr, src + off, nullptr, 0);
-    c = deflate<false>(w, n, max_dist(wb));
+    __shared__ __attribute__((aligned(16))) uint32_t s_Tm[kTab];
+    __shared__ __attribute__((aligned(16))) uint32_t s_scrm[kScrWords];
+    s_T = s_Tm, s_scr = s_scrm;
   }
-  const bool plain = (flags & GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER) && c >= n;
-  const uint64_t wire = plain ? n : c;
-  if (threadIdx.x == 0) {
-    rec[m] = DefRec{(uint32_t)wire, plain ? 1u : 0u};
-    blk[m * kBlkFields + 0] = 1;
-    blk[m * kBlkFields + 1] = round16(wire);
-    blk[m * kBlkFields + 2] = wire;
+  const uint64_t m = def_block_message<CTX>();
+  const uint64_t cnt = gated_count(max_msgs, gate);
+  if (m >= cnt) return;  // (blk and rec are zeroed)
+  if constexpr (CTX) {
+    const uint32_t c = uniform32(msg_conn[m]);
+    if (c >= n_conns) {  // never an index: the call is GEVWS_ERR_INVALID (k_def_verdict)
+      if (threadIdx.x == 0) blk[m * kBlkFields + 3] = 1;
+      return;
+    }
+    if (uniform32(conn_ext[c]) & GEVWS_EXT_SERVER_TAKEOVER) {  // wave-uniform
+      if (m && uniform32(msg_conn[m - 1]) == c) return;  // the run's first message walks the run
+      // a second run of the connection: two waves would race on its slot
+      uint32_t runs = 0;
+      if (threadIdx.x == 0) runs = atomicAdd(heads + c, 1u);
+      if (uniform32(runs) != 0) {
+        if (threadIdx.x == 0) blk[m * kBlkFields + 3] = 1;
+        return;
+      }
+      uint64_t total = def_load_slot(def_ctx + (uint64_t)c * GEVWS_DEF_CTX_BYTES, s_ring, s_tab);
+      for (uint64_t k = m; k < cnt; ++k) {  // (at most the run's messages)
+        if (k != m && uniform32(msg_conn[k]) != c) break;
+        bool bad;
+        total = def_size_one<DYN, true>(k, msgs, src, src_bytes, flags, blk, rec, s_ring, s_tab, s_T, s_scr, total,
+                                        bad);
+      }
+      return;
+    }
   }
+  bool bad;
+  (void)def_size_one<DYN, false>(m, msgs, src, src_bytes, flags, blk, rec, s_ring, s_tab, s_T, s_scr, 0, bad);
 }
 
 // ------------------------------------------------------------------ 2. a malformed record fails the call
@@ -433,7 +595,49 @@ __global__ void k_def_verdict(gevws_summary* __restrict__ sum) {
 }
 
 // ------------------------------------------------------------------ 3. the bytes and the records
-template <bool DYN>
+struct DefEmitLds {
+  uint32_t *ring, *out, *T, *match;
+  uint16_t* tab;
+  uint64_t *lm, *tm;
+};
+
+// Message k's payload.  CHAIN: as in def_size_one.
+template <bool DYN, bool CHAIN>
+__device__ __forceinline__ uint64_t def_emit_one(const gevws_deflate_msg& msg, const DefRec& r, uint64_t base,
+                                                 const uint8_t* __restrict__ src, uint8_t* __restrict__ d_out,
+                                                 const DefEmitLds& s, uint64_t total) {
+  const uint64_t off = uniform64(msg.payload_off), n = uniform64(msg.length);
+  const uint32_t wire = uniform32(r.wire), plain = uniform32(r.plain);
+  const uint8_t* __restrict__ p = src + off;
+  uint8_t* __restrict__ q = d_out + base;
+  if (!CHAIN && plain) {  // verbatim, the last vector's pad zeroed
+    for (uint64_t o = 16 * (uint64_t)threadIdx.x; o < n; o += 16 * kDefBlock) {
+      u32x4 v = *reinterpret_cast<const u32x4*>(p + o);
+      if (n - o < 16) v = keep_bytes(v, (int64_t)(n - o));
+      *reinterpret_cast<u32x4*>(q + o) = v;
+    }
+    return total;
+  }
+  if constexpr (!CHAIN) {
+    for (uint32_t j = threadIdx.x; j < kHashSlots / 8; j += kDefBlock)
+      reinterpret_cast<u32x4*>(s.tab)[j] = u32x4{0, 0, 0, 0};
+  }
+  for (uint32_t j = threadIdx.x; j < kOutWords / 4; j += kDefBlock)
+    reinterpret_cast<u32x4*>(s.out)[j] = u32x4{0, 0, 0, 0};
+  wave_lds_order();
+  // the sized length bounds the slot: the wave never writes past its allotted bytes
+  if constexpr (DYN) {
+    DefWaveDyn<true, CHAIN> w(s.ring, s.tab, s.out, p, q, round16(wire), s.T, s.out + kScrAt, s.lm, s.tm, s.match,
+                              total);
+    (void)deflate_dyn<true>(w, n, max_dist(uniform32(msg.window_bits)), total);
+  } else {
+    DefWave<true, CHAIN> w(s.ring, s.tab, s.out, p, q, round16(wire), total);
+    (void)deflate<true>(w, n, max_dist(uniform32(msg.window_bits)), total);
+  }
+  return total + n;
+}
+
+template <bool DYN, bool CTX>
 __global__ __launch_bounds__(kDefBlock) void k_def_emit(const gevws_deflate_msg* __restrict__ msgs, uint64_t max_msgs,
                                                         const gevws_summary* __restrict__ gate,
                                                         const uint8_t* __restrict__ src,
@@ -441,19 +645,29 @@ __global__ __launch_bounds__(kDefBlock) void k_def_emit(const gevws_deflate_msg*
                                                         const DefRec* __restrict__ rec,
                                                         const gevws_summary* __restrict__ sum,
                                                         gevws_out_frame* __restrict__ frames,
-                                                        uint8_t* __restrict__ d_out) {
+                                                        uint8_t* __restrict__ d_out,
+                                                        const uint32_t* __restrict__ msg_conn,
+                                                        const uint8_t* __restrict__ conn_ext, uint8_t* def_ctx) {
   __shared__ __attribute__((aligned(16))) uint32_t s_ring[kRingWords];
   __shared__ __attribute__((aligned(16))) uint16_t s_tab[kHashSlots];
   __shared__ __attribute__((aligned(16))) uint32_t s_out[kOutWords];
-  if (sum->status != GEVWS_OK) return;  // capacity or a malformed record: nothing written
-  const uint64_t m = blockIdx.x;
-  if (m >= gated_count(max_msgs, gate)) return;
+  DefEmitLds s{s_ring, s_out, nullptr, nullptr, s_tab, nullptr, nullptr};
+  if constexpr (DYN) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_T[kTab];
+    __shared__ __attribute__((aligned(16))) uint64_t s_lm[kMaskWords];
+    __shared__ __attribute__((aligned(16))) uint64_t s_tm[kMaskWords];
+    __shared__ __attribute__((aligned(16))) uint32_t s_match[kMaxMatches];
+    s.T = s_T, s.lm = s_lm, s.tm = s_tm, s.match = s_match;
+  }
+  if (sum->status != GEVWS_OK) return;  // capacity or a malformed record: nothing written, the slots untouched
+  const uint64_t m = def_block_message<CTX>();
+  const uint64_t cnt = gated_count(max_msgs, gate);
+  if (m >= cnt) return;
   const gevws_deflate_msg msg = msgs[m];
   const DefRec r = rec[m];
   const uint64_t base = uniform64(blk[m * kBlkFields + 1]);  // (exclusive after the scan)
-  const uint64_t off = uniform64(msg.payload_off), n = uniform64(msg.length);
-  const uint32_t wire = uniform32(r.wire), plain = uniform32(r.plain);
   if (threadIdx.x == 0) {
+    const uint32_t wire = uniform32(r.wire), plain = uniform32(r.plain);
     gevws_out_frame o;
     memset(&o, 0, sizeof(o));
     o.hdr.fin = 1;
@@ -464,43 +678,50 @@ __global__ __launch_bounds__(kDefBlock) void k_def_emit(const gevws_deflate_msg*
     o.payload_len = wire;
     frames[m] = o;
   }
-  const uint8_t* __restrict__ p = src + off;
-  uint8_t* __restrict__ q = d_out + base;
-  if (plain) {  // verbatim, the last vector's pad zeroed
-    for (uint64_t o = 16 * (uint64_t)threadIdx.x; o < n; o += 16 * kDefBlock) {
-      u32x4 v = *reinterpret_cast<const u32x4*>(p + o);
-      if (n - o < 16) v = keep_bytes(v, (int64_t)(n - o));
-      *reinterpret_cast<u32x4*>(q + o) = v;
+  if constexpr (CTX) {
+    const uint32_t c = uniform32(msg_conn[m]);  // (below n_conns, or the summary were INVALID)
+    if (uniform32(conn_ext[c]) & GEVWS_EXT_SERVER_TAKEOVER) {  // wave-uniform
+      if (m && uniform32(msg_conn[m - 1]) == c) return;  // the run's first message walks the run
+      uint8_t* slot = def_ctx + (uint64_t)c * GEVWS_DEF_CTX_BYTES;
+      const uint64_t total0 = def_load_slot(slot, s_ring, s_tab);
+      uint64_t total = total0;
+      for (uint64_t k = m; k < cnt; ++k) {  // (at most the run's messages)
+        if (k != m && uniform32(msg_conn[k]) != c) break;
+        total = def_emit_one<DYN, true>(msgs[k], rec[k], uniform64(blk[k * kBlkFields + 1]), src, d_out, s, total);
+      }
+      if (total == total0) return;  // only empty messages: the slot stays as it is
+      wave_lds_order();
+      // stream bytes [total0, total), at most the last 32 KiB of them, as whole
+      // vectors (the stage merged their other bytes: the slot's own, or zeros
+      // where the stream has not reached yet), the table and the head
+      const uint32_t lane = threadIdx.x & 63;
+      uint64_t x = total - total0 >= kWin ? total - kWin : total0;
+      for (x = (x & ~15ull) + 16 * lane; x < total; x += 16 * kDefBlock) {
+        const uint32_t o = (uint32_t)x & (kWin - 1);
+        *reinterpret_cast<u32x4*>(slot + kCtxHead + o) = *reinterpret_cast<const u32x4*>(s_ring + (o >> 2));
+      }
+      for (uint32_t j = lane; j < kHashSlots / 8; j += kDefBlock)
+        reinterpret_cast<u32x4*>(slot + kCtxHead + kWin)[j] = reinterpret_cast<const u32x4*>(s_tab)[j];
+      if (lane == 0) *reinterpret_cast<uint64_t*>(slot) = total;
+      return;
     }
-    return;
   }
-  for (uint32_t j = threadIdx.x; j < kHashSlots / 8; j += kDefBlock)
-    reinterpret_cast<u32x4*>(s_tab)[j] = u32x4{0, 0, 0, 0};
-  for (uint32_t j = threadIdx.x; j < kOutWords / 4; j += kDefBlock)
-    reinterpret_cast<u32x4*>(s_out)[j] = u32x4{0, 0, 0, 0};
-  wave_lds_order();
-  // the sized length bounds the slot: the wave never writes past its allotted bytes
-  if constexpr (DYN) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_T[kTab];
-    __shared__ __attribute__((aligned(16))) uint64_t s_lm[kMaskWords];
-    __shared__ __attribute__((aligned(16))) uint64_t s_tm[kMaskWords];
-    __shared__ __attribute__((aligned(16))) uint32_t s_match[kMaxMatches];
-    DefWaveDyn<true> w(s_ring, s_tab, s_out, p, q, round16(wire), s_T, s_out + kScrAt, s_lm, s_tm, s_match);
-    (void)deflate_dyn<true>(w, n, max_dist(uniform32(msg.window_bits)));
-  } else {
-    DefWave<true> w(s_ring, s_tab, s_out, p, q, round16(wire));
-    (void)deflate<true>(w, n, max_dist(uniform32(msg.window_bits)));
-  }
+  (void)def_emit_one<DYN, false>(msg, r, base, src, d_out, s, 0);
 }
 
 }  // namespace
 
 using namespace gevws_impl;
 
-extern "C" int gevws_deflate_async(gevws_ctx* ctx, void* stream, const gevws_deflate_msg* d_msgs, uint64_t max_msgs,
-                                   const gevws_summary* d_prev, const uint8_t* d_src, uint64_t src_bytes,
-                                   uint32_t flags, gevws_out_frame* d_out_frames, uint8_t* d_out, uint64_t out_cap,
-                                   gevws_summary* d_summary) {
+extern "C" int gevws_deflate_ctx_async(gevws_ctx* ctx, void* stream, const gevws_deflate_msg* d_msgs,
+                                       uint64_t max_msgs, const gevws_summary* d_prev, const uint8_t* d_src,
+                                       uint64_t src_bytes, uint32_t flags, gevws_out_frame* d_out_frames,
+                                       uint8_t* d_out, uint64_t out_cap, gevws_summary* d_summary,
+                                       const uint32_t* d_msg_conn, const uint8_t* d_conn_ext, uint8_t* d_def_ctx,
+                                       uint32_t n_conns) {
+  const bool with_ctx = d_msg_conn && d_conn_ext && d_def_ctx;  // any NULL: gevws_deflate_async, bit for bit
+  if (with_ctx && ((reinterpret_cast<uintptr_t>(d_def_ctx) & 15) || max_msgs > 0x7FF00000ull))
+    return GEVWS_ERR_INVALID;
   if (!ctx || !d_summary || max_msgs > 0x7FFFFFFFull ||
       (flags & ~(GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER | GEVWS_DEFLATE_DYNAMIC)))
     return GEVWS_ERR_INVALID;
@@ -513,22 +734,52 @@ extern "C" int gevws_deflate_async(gevws_ctx* ctx, void* stream, const gevws_def
   if (!d_msgs || !d_src || !d_out_frames || !d_out) return GEVWS_ERR_INVALID;
   int r = order_after_last(ctx, st);
   if (r != GEVWS_OK) return r;
-  r = ensure_scratch(ctx, def_scratch(nullptr, max_msgs).total);
+  const uint32_t nc = with_ctx ? n_conns : 0;
+  r = ensure_scratch(ctx, def_scratch(nullptr, max_msgs, nc).total);
   if (r != GEVWS_OK) return r;
-  const DefScratch s = def_scratch(ctx->scratch, max_msgs);
+  const DefScratch s = def_scratch(ctx->scratch, max_msgs, nc);
   GEVWS_HIP(hipMemsetAsync(ctx->scratch, 0, s.total, st));
   const uint32_t nm = (uint32_t)max_msgs;
+  const uint32_t ng = kDefSpread * def_grid_q(nm);  // the grid with contexts (def_block_message)
   const bool dyn = flags & GEVWS_DEFLATE_DYNAMIC;
-  if (dyn) k_def_size<true><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, src_bytes, flags, s.blk, s.rec);
-  else k_def_size<false><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, src_bytes, flags, s.blk, s.rec);
+  if (with_ctx) {
+    if (dyn)
+      k_def_size<true, true><<<ng, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, src_bytes, flags, s.blk, s.rec,
+                                                       d_msg_conn, d_conn_ext, d_def_ctx, n_conns, s.heads);
+    else
+      k_def_size<false, true><<<ng, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, src_bytes, flags, s.blk,
+                                                        s.rec, d_msg_conn, d_conn_ext, d_def_ctx, n_conns, s.heads);
+  } else if (dyn) {
+    k_def_size<true, false><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, src_bytes, flags, s.blk, s.rec,
+                                                      nullptr, nullptr, nullptr, 0, nullptr);
+  } else {
+    k_def_size<false, false><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, src_bytes, flags, s.blk, s.rec,
+                                                       nullptr, nullptr, nullptr, 0, nullptr);
+  }
   k_scan_blocks<false><<<1, kScanBlock, 0, st>>>(s.blk, nm, UINT64_MAX, out_cap, d_summary);
   k_def_verdict<<<1, 1, 0, st>>>(d_summary);
-  if (dyn)
-    k_def_emit<true><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, s.blk, s.rec, d_summary, d_out_frames,
-                                               d_out);
-  else
-    k_def_emit<false><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, s.blk, s.rec, d_summary, d_out_frames,
-                                                d_out);
+  if (with_ctx) {
+    if (dyn)
+      k_def_emit<true, true><<<ng, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, s.blk, s.rec, d_summary,
+                                                       d_out_frames, d_out, d_msg_conn, d_conn_ext, d_def_ctx);
+    else
+      k_def_emit<false, true><<<ng, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, s.blk, s.rec, d_summary,
+                                                        d_out_frames, d_out, d_msg_conn, d_conn_ext, d_def_ctx);
+  } else if (dyn) {
+    k_def_emit<true, false><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, s.blk, s.rec, d_summary,
+                                                      d_out_frames, d_out, nullptr, nullptr, nullptr);
+  } else {
+    k_def_emit<false, false><<<nm, kDefBlock, 0, st>>>(d_msgs, max_msgs, d_prev, d_src, s.blk, s.rec, d_summary,
+                                                       d_out_frames, d_out, nullptr, nullptr, nullptr);
+  }
   GEVWS_HIP(hipGetLastError());
   return mark_last(ctx, st);
+}
+
+extern "C" int gevws_deflate_async(gevws_ctx* ctx, void* stream, const gevws_deflate_msg* d_msgs, uint64_t max_msgs,
+                                   const gevws_summary* d_prev, const uint8_t* d_src, uint64_t src_bytes,
+                                   uint32_t flags, gevws_out_frame* d_out_frames, uint8_t* d_out, uint64_t out_cap,
+                                   gevws_summary* d_summary) {
+  return gevws_deflate_ctx_async(ctx, stream, d_msgs, max_msgs, d_prev, d_src, src_bytes, flags, d_out_frames, d_out,
+                                 out_cap, d_summary, nullptr, nullptr, nullptr, 0);
 }

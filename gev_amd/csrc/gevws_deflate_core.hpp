@@ -3,7 +3,18 @@
 // device (one wave per message, gevws_deflate.hip) and the host
 // (gevws_deflate_raw, the fuzz programs).  Fixed-Huffman and stored blocks,
 // dynamic-Huffman blocks too with GEVWS_DEFLATE_DYNAMIC (the second half of
-// this file), greedy LZ77 with one candidate per hash slot, no context takeover.
+// this file), greedy LZ77 with one candidate per hash slot.
+//
+// Context takeover.  A message may continue a connection's stream: it starts
+// at stream position B (0 without a context), and every position below is a
+// STREAM position -- message byte p is stream byte B + p, it sits at ring byte
+// (B + p) mod 32 768 and its hash slot holds (B + p) mod 65 536.  The ring and
+// the hash table are then the connection's, carried from message to message
+// (gevws_deflate_ctx_async, gevws_deflate_raw_ctx): the table is not cleared,
+// and a match may reach back across the message's first byte into history.
+// Runs and steps still count from the message's first byte, and the last three
+// positions of a message are not hashed (the next message is not known).
+// B = 0 over an all-zero table is the compressor without a context, bit for bit.
 //
 // The algorithm is defined in steps of 64 consecutive positions so that a wave
 // and a host loop make the same choices, byte for byte:
@@ -14,7 +25,8 @@
 //   step    At p0 the positions p0 .. p0 + cnt - 1 (cnt <= 64, inside the
 //           run) each hash the 4 bytes at p (when the message has them), read
 //           the slot's candidate as it was BEFORE the step, and take
-//           d = (p - candidate) mod 65 536 when 1 <= d <= min(p, maxd); the
+//           d = (p - candidate) mod 65 536 when 1 <= d <= min(p, maxd) (p the
+//           stream position: history counts); the
 //           match length is the common prefix of p and p - d, at most 258 and
 //           at most the rest of the run; below 3 it is no match.  A second
 //           candidate is the step's LOWEST position with the same slot (a run
@@ -34,8 +46,8 @@
 //           into zeroed output.
 //
 // The driver below is generic over a W that holds the lanes:
-//   void stage(p0, n)                       the input up to p0 + 64 + 258 + 8 is at hand
-//   void find(p0, cnt, run_end, n, maxd)    the step's lookups, extensions and inserts
+//   void stage(p0, end)                     the input up to p0 + 64 + 258 + 8 is at hand (end: the message's)
+//   void find(p0, cnt, run_end, end, maxd)  the step's lookups, extensions and inserts
 //   uint64_t match_mask()                   positions (bit i: p0 + i) with a match
 //   uint32_t len_at(i)                      its length
 //   uint32_t tokens<EMIT>(lits, take, bit)  the bits of the step's tokens; writes them at `bit`
@@ -201,10 +213,11 @@ GEVWS_DEF_HD uint32_t choose(W& w, uint32_t cnt, uint64_t& lits, uint64_t& take)
 
 // The whole message: its compressed length in bytes; with EMIT the bytes too.
 template <bool EMIT, class W>
-GEVWS_DEF_HD uint64_t deflate(W& w, uint64_t n, uint32_t maxd) {
+GEVWS_DEF_HD uint64_t deflate(W& w, uint64_t n, uint32_t maxd, uint64_t B = 0) {
   uint64_t bit = 0;
-  for (uint64_t rs = 0; rs < n; rs += kRun) {
-    const uint32_t rl = n - rs < kRun ? (uint32_t)(n - rs) : kRun;
+  const uint64_t end = B + n;
+  for (uint64_t rs = B; rs < end; rs += kRun) {
+    const uint32_t rl = end - rs < kRun ? (uint32_t)(end - rs) : kRun;
     const uint64_t run_end = rs + rl, bit0 = bit;
     if (EMIT) {
       w.begin_run(bit0);
@@ -214,8 +227,8 @@ GEVWS_DEF_HD uint64_t deflate(W& w, uint64_t n, uint32_t maxd) {
     uint64_t p0 = rs;
     while (p0 < run_end) {
       const uint32_t cnt = run_end - p0 < kLanes ? (uint32_t)(run_end - p0) : kLanes;
-      w.stage(p0, n);
-      w.find(p0, cnt, run_end, n, maxd);
+      w.stage(p0, end);
+      w.find(p0, cnt, run_end, end, maxd);
       uint64_t lits, take;
       const uint32_t pos = choose(w, cnt, lits, take);
       bit += w.template tokens<EMIT>(lits, take, bit);
@@ -556,19 +569,20 @@ GEVWS_DEF_HD DynHeader dyn_code(W& w, uint32_t* T, uint32_t* scr) {
 
 // The whole message with GEVWS_DEFLATE_DYNAMIC.
 template <bool EMIT, class W>
-GEVWS_DEF_HD uint64_t deflate_dyn(W& w, uint64_t n, uint32_t maxd) {
+GEVWS_DEF_HD uint64_t deflate_dyn(W& w, uint64_t n, uint32_t maxd, uint64_t B = 0) {
   uint64_t bit = 0;
+  const uint64_t end = B + n;
   uint32_t* T = w.table();
   uint32_t* scr = w.scratch();
-  for (uint64_t rs = 0; rs < n; rs += kRun) {
-    const uint32_t rl = n - rs < kRun ? (uint32_t)(n - rs) : kRun;
+  for (uint64_t rs = B; rs < end; rs += kRun) {
+    const uint32_t rl = end - rs < kRun ? (uint32_t)(end - rs) : kRun;
     const uint64_t run_end = rs + rl, bit0 = bit;
     w.begin_dyn();
     uint64_t p0 = rs;
     while (p0 < run_end) {
       const uint32_t cnt = run_end - p0 < kLanes ? (uint32_t)(run_end - p0) : kLanes;
-      w.stage(p0, n);
-      w.find(p0, cnt, run_end, n, maxd);
+      w.stage(p0, end);
+      w.find(p0, cnt, run_end, end, maxd);
       uint64_t lits, take;
       const uint32_t pos = choose(w, cnt, lits, take);
       w.template note<EMIT>(lits, take, (uint32_t)(p0 - rs));

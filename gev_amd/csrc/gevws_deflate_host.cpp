@@ -1,7 +1,9 @@
 // gevws_deflate_host.cpp -- gevws_deflate_raw, gevws_deflate_raw_flags and gevws_deflate_bound
 // (include/gevws.h): the compressor of gevws_deflate_core.hpp on host memory,
-// the 64 positions of a step taken one after the other.  Plain C++: it also
-// builds outside the library, under sanitizers (tests/cpp/deflate_fuzz.cpp).
+// the 64 positions of a step taken one after the other, and gevws_deflate_raw_ctx,
+// the same over one connection's context slot (server context takeover).  Plain
+// C++: it also builds outside the library, under sanitizers
+// (tests/cpp/deflate_fuzz.cpp, tests/cpp/deflate_ctx_fuzz.cpp).
 #include <cstring>
 
 #include "gevws.h"
@@ -14,14 +16,24 @@ using namespace gevws_deflate;
 // A run's bits before they are final: a fixed block of kRun 9-bit literals,
 // the partial byte before it and the step's slack.
 constexpr uint32_t kOutBytes = kRun + kRun / 8 + 128;
+// the slot (include/gevws.h): a 64-byte head, the ring image, the hash table
+constexpr uint32_t kCtxHead = 64;
+static_assert(GEVWS_DEF_CTX_BYTES == kCtxHead + kWin + kHashSlots * 2, "the deflate slot");
 
 struct HostW {
+  // Positions are stream positions: the message is stream bytes [B, B + n), and
+  // what lies before B is read from the slot's ring as the call found it.
   struct Reader {
     const uint8_t* in;
-    uint64_t n;
-    uint32_t u32(uint64_t pos) const {  // zeros past the message (the core clamps before they count)
+    uint64_t n, B;
+    const uint8_t* ring;  // with B > 0: stream byte i at ring[i & 32767]
+    uint8_t at(uint64_t pos) const {  // zeros past the message (the core clamps before they count)
+      if (pos < B) return ring[pos & (kWin - 1)];
+      return pos - B < n ? in[pos - B] : 0;
+    }
+    uint32_t u32(uint64_t pos) const {
       uint32_t v = 0;
-      for (uint32_t i = 0; i < 4 && pos + i < n; ++i) v |= (uint32_t)in[pos + i] << (8 * i);
+      for (uint32_t i = 0; i < 4; ++i) v |= (uint32_t)at(pos + i) << (8 * i);
       return v;
     }
     uint64_t u64(uint64_t pos) const { return (uint64_t)u32(pos) | ((uint64_t)u32(pos + 4) << 32); }
@@ -34,8 +46,11 @@ struct HostW {
   uint32_t len[kLanes], dist[kLanes];
   uint8_t obuf[kOutBytes];
 
-  HostW(const uint8_t* in, uint64_t n, uint8_t* out_) : rd{in, n}, out(out_) {
-    memset(tab, 0, sizeof(tab));
+  // slot: the connection's context (its table is copied: the slot is written by the caller alone)
+  HostW(const uint8_t* in, uint64_t n, uint8_t* out_, const uint8_t* slot = nullptr, uint64_t B = 0)
+      : rd{in, n, B, slot ? slot + kCtxHead : nullptr}, out(out_) {
+    if (slot) memcpy(tab, slot + kCtxHead + kWin, sizeof(tab));
+    else memset(tab, 0, sizeof(tab));
     memset(obuf, 0, sizeof(obuf));
   }
   void stage(uint64_t, uint64_t) {}
@@ -73,7 +88,7 @@ struct HostW {
     uint32_t total = 0;
     for (uint32_t l = 0; l < cnt; ++l) {
       uint32_t nb = 0, code = 0;
-      if ((lits >> l) & 1) code = lit_code(rd.in[p0 + l], nb);
+      if ((lits >> l) & 1) code = lit_code(rd.at(p0 + l), nb);
       else if ((take >> l) & 1) code = match_code(len[l], dist[l], nb);
       if (EMIT && nb) or_bits(bit + total, code);
       total += nb;
@@ -87,7 +102,7 @@ struct HostW {
     memset(obuf + (o >> 3) + 1, 0, sizeof(obuf) - (o >> 3) - 1);
   }
   void put_bits(uint64_t bit, uint32_t v, uint32_t) { or_bits(bit, v); }
-  void stored(uint64_t src, uint32_t n, uint64_t byte) { memcpy(obuf + (byte - flushed), rd.in + src, n); }
+  void stored(uint64_t src, uint32_t n, uint64_t byte) { memcpy(obuf + (byte - flushed), rd.in + (src - rd.B), n); }
   void end_run(uint64_t bit) {
     const uint64_t whole = (bit >> 3) - flushed;
     memcpy(out + flushed, obuf, whole);
@@ -111,7 +126,8 @@ struct HostDynW : HostW, SerialSteps {
   uint32_t match[kMaxMatches];
   uint32_t nmatch = 0;
 
-  HostDynW(const uint8_t* in, uint64_t n, uint8_t* out_) : HostW(in, n, out_) {}
+  HostDynW(const uint8_t* in, uint64_t n, uint8_t* out_, const uint8_t* slot = nullptr, uint64_t B = 0)
+      : HostW(in, n, out_, slot, B) {}
   uint32_t* table() { return tab32; }
   uint32_t* scratch() { return scr; }
   void begin_dyn() {
@@ -124,7 +140,7 @@ struct HostDynW : HostW, SerialSteps {
   void note(uint64_t lits, uint64_t take, uint32_t q) {
     for (uint32_t l = 0; l < cnt; ++l) {
       if ((lits >> l) & 1) {
-        ++tab32[rd.in[p0 + l]];
+        ++tab32[rd.at(p0 + l)];
       } else if ((take >> l) & 1) {
         uint32_t eb, ev;
         ++tab32[257 + len_sym(len[l], eb, ev)];
@@ -155,7 +171,7 @@ struct HostDynW : HostW, SerialSteps {
     for (uint32_t i = 0; i < rl; ++i) {
       if ((lm[i >> 6] >> (i & 63)) & 1) {
         uint32_t nb;
-        const uint32_t code = dyn_lit(tab32, rd.in[rs + i], nb);
+        const uint32_t code = dyn_lit(tab32, rd.at(rs + i), nb);
         or_bits(bit + total, code);
         total += nb;
       } else if ((tm[i >> 6] >> (i & 63)) & 1) {
@@ -171,21 +187,34 @@ struct HostDynW : HostW, SerialSteps {
   }
 };
 
+// slot: NULL, or the connection's context: both passes start from it as it
+// stands (each on a copy of its table), and only a message that fits is
+// appended to it -- the ring, the table as the emitting pass left it, the head.
 template <class W, bool DYN>
-int run(const uint8_t* in, uint64_t n, uint32_t maxd, uint8_t* out, uint64_t cap, uint64_t* out_len) {
+int run(const uint8_t* in, uint64_t n, uint32_t maxd, uint8_t* out, uint64_t cap, uint64_t* out_len,
+        uint8_t* slot = nullptr) {
+  uint64_t B = 0;
+  if (slot) memcpy(&B, slot, sizeof(B));
   uint64_t need;
   {
-    W w(in, n, nullptr);
-    if constexpr (DYN) need = deflate_dyn<false>(w, n, maxd);
-    else need = deflate<false>(w, n, maxd);
+    W w(in, n, nullptr, slot, B);
+    if constexpr (DYN) need = deflate_dyn<false>(w, n, maxd, B);
+    else need = deflate<false>(w, n, maxd, B);
   }
   if (out_len) *out_len = need;
   if (need > cap) return GEVWS_ERR_CAPACITY;
-  W w(in, n, out);
+  W w(in, n, out, slot, B);
   uint64_t got;
-  if constexpr (DYN) got = deflate_dyn<true>(w, n, maxd);
-  else got = deflate<true>(w, n, maxd);
-  return got == need ? GEVWS_OK : GEVWS_ERR_INVALID;  // (the two passes are one algorithm)
+  if constexpr (DYN) got = deflate_dyn<true>(w, n, maxd, B);
+  else got = deflate<true>(w, n, maxd, B);
+  if (got != need) return GEVWS_ERR_INVALID;  // (the two passes are one algorithm)
+  if (slot && n) {
+    for (uint64_t i = n > kWin ? n - kWin : 0; i < n; ++i) slot[kCtxHead + ((B + i) & (kWin - 1))] = in[i];
+    memcpy(slot + kCtxHead + kWin, w.tab, sizeof(w.tab));
+    B += n;
+    memcpy(slot, &B, sizeof(B));
+  }
+  return GEVWS_OK;
 }
 
 }  // namespace
@@ -201,6 +230,17 @@ extern "C" int gevws_deflate_raw_flags(const uint8_t* in, uint64_t n, int window
   const uint32_t maxd = max_dist((uint32_t)window_bits);
   if (flags & GEVWS_DEFLATE_DYNAMIC) return run<HostDynW, true>(in, n, maxd, out, cap, out_len);
   return run<HostW, false>(in, n, maxd, out, cap, out_len);
+}
+
+extern "C" int gevws_deflate_raw_ctx(const uint8_t* in, uint64_t n, int window_bits, uint32_t flags, uint8_t* out,
+                                     uint64_t cap, uint64_t* out_len, uint8_t* ctx) {
+  if (out_len) *out_len = 0;
+  if (!ctx || (n && !in) || (cap && !out) || n > 0xFFFFFFFFull ||
+      (window_bits != 0 && (window_bits < 8 || window_bits > 15)) || (flags & ~GEVWS_DEFLATE_DYNAMIC))
+    return GEVWS_ERR_INVALID;
+  const uint32_t maxd = max_dist((uint32_t)window_bits);
+  if (flags & GEVWS_DEFLATE_DYNAMIC) return run<HostDynW, true>(in, n, maxd, out, cap, out_len, ctx);
+  return run<HostW, false>(in, n, maxd, out, cap, out_len, ctx);
 }
 
 extern "C" int gevws_deflate_raw(const uint8_t* in, uint64_t n, int window_bits, uint8_t* out, uint64_t cap,

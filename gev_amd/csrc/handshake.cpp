@@ -660,8 +660,10 @@ bool window_bits(const std::string& v, int* bits) {
 }
 }  // namespace
 
-std::string DeflateAnswer(const uint8_t* offer, uint64_t n, bool client_takeover, bool* client_keeps) {
+std::string DeflateAnswer(const uint8_t* offer, uint64_t n, bool client_takeover, bool* client_keeps,
+                          bool server_takeover, bool* server_keeps) {
   if (client_keeps) *client_keeps = false;
+  if (server_keeps) *server_keeps = false;
   std::vector<ExtOption> opts;
   if (!scan_options(Bytes{offer, n}, &opts)) return "";
   for (const ExtOption& o : opts) {
@@ -687,8 +689,11 @@ std::string DeflateAnswer(const uint8_t* offer, uint64_t n, bool client_takeover
     if (!ok) continue;
     const bool keeps = client_takeover && !seen[1];  // (an offer that carried the parameter gets it echoed)
     if (client_keeps) *client_keeps = keeps;
-    std::string a = keeps ? "permessage-deflate; server_no_context_takeover"
-                          : "permessage-deflate; client_no_context_takeover; server_no_context_takeover";
+    const bool skeeps = server_takeover && !seen[0];  // (likewise, RFC 7692 section 7.1.1.1)
+    if (server_keeps) *server_keeps = skeeps;
+    std::string a = "permessage-deflate";
+    if (!keeps) a += "; client_no_context_takeover";
+    if (!skeeps) a += "; server_no_context_takeover";
     if (seen[2]) a += "; server_max_window_bits=" + std::to_string(server_bits);
     return a;
   }
@@ -708,6 +713,24 @@ extern "C" int gevws_deflate_negotiate_flags(const uint8_t* offer, uint64_t n, u
   if (!a.empty()) memcpy(out, a.data(), a.size());
   *out_len = a.size();
   if (conn_ext && !a.empty()) *conn_ext = (uint8_t)(GEVWS_EXT_DEFLATE | (keeps ? GEVWS_EXT_CLIENT_TAKEOVER : 0u));
+  return GEVWS_OK;
+}
+
+extern "C" int gevws_deflate_negotiate_takeover(const uint8_t* offer, uint64_t n, uint32_t flags, uint8_t* out,
+                                                uint64_t cap, uint64_t* out_len, uint8_t* conn_ext) {
+  if (out_len) *out_len = 0;
+  if (conn_ext) *conn_ext = 0;
+  if ((n && !offer) || !out_len || (flags & ~(GEVWS_NEGOTIATE_CLIENT_TAKEOVER | GEVWS_NEGOTIATE_SERVER_TAKEOVER)))
+    return GEVWS_ERR_INVALID;
+  bool keeps = false, skeeps = false;
+  const std::string a = gevws::DeflateAnswer(offer, n, flags & GEVWS_NEGOTIATE_CLIENT_TAKEOVER, &keeps,
+                                             flags & GEVWS_NEGOTIATE_SERVER_TAKEOVER, &skeeps);
+  if (a.size() > cap || (a.size() && !out)) return GEVWS_ERR_CAPACITY;
+  if (!a.empty()) memcpy(out, a.data(), a.size());
+  *out_len = a.size();
+  if (conn_ext && !a.empty())
+    *conn_ext = (uint8_t)(GEVWS_EXT_DEFLATE | (keeps ? GEVWS_EXT_CLIENT_TAKEOVER : 0u) |
+                          (skeeps ? GEVWS_EXT_SERVER_TAKEOVER : 0u));
   return GEVWS_OK;
 }
 

@@ -45,8 +45,9 @@ class Upgrader {
 // `offer` that needs no context takeover of the server; "" when there is none.
 // With client_takeover the answer leaves client_no_context_takeover out unless
 // the offer carried it; *client_keeps says whether the client may keep its
-// window (gevws_deflate_negotiate_flags).
+// window (gevws_deflate_negotiate_flags).  Likewise server_takeover,
+// server_no_context_takeover and *server_keeps (gevws_deflate_negotiate_takeover).
 std::string DeflateAnswer(const uint8_t* offer, uint64_t n, bool client_takeover = false,
-                          bool* client_keeps = nullptr);
+                          bool* client_keeps = nullptr, bool server_takeover = false, bool* server_keeps = nullptr);
 
 }  // namespace gevws

@@ -804,6 +804,101 @@ int gevws_deflate_raw(const uint8_t *in, uint64_t n, int window_bits,
 int gevws_deflate_raw_flags(const uint8_t *in, uint64_t n, int window_bits, uint32_t flags,
                             uint8_t *out, uint64_t cap, uint64_t *out_len);
 
+/* Server context takeover: the deflate step with a window and a hash table
+ * per connection, kept between messages and between calls.  Additions to ABI
+ * version 3: nothing above changes.
+ *
+ * GEVWS_EXT_SERVER_TAKEOVER is a third bit of the d_conn_ext byte, set beside
+ * GEVWS_EXT_DEFLATE for a connection whose answer left
+ * server_no_context_takeover out (gevws_deflate_negotiate_takeover says when).
+ * The message pass masks the byte with GEVWS_EXT_DEFLATE and the inflate step
+ * tests GEVWS_EXT_CLIENT_TAKEOVER only: neither sees the new bit.
+ *
+ * The slot.  d_def_ctx is a caller-owned device buffer of n_conns slots of
+ * GEVWS_DEF_CTX_BYTES each, on a 16-byte boundary; connection c's is slot c.
+ * All-zero is a fresh connection.  Callers treat a slot as opaque; its layout
+ * is a 64-byte head -- uint64 total (little-endian: the plain bytes of the
+ * connection's compressed messages so far), zeros --, behind it the ring
+ * image: stream byte i sits at ring[i & 32767] for the last min(total, 32 768)
+ * stream bytes, bytes never written stay zero; and behind that the compressor's
+ * hash table, 4 096 slots of 16 bits (little-endian), as the connection's
+ * last step left it.  A slot's content is a function of the connection's
+ * sequence of compressed messages (their bytes and window_bits; the call's
+ * GEVWS_DEFLATE_DYNAMIC does not change it: the tokens are the same) -- not
+ * of how the messages were cut into calls, the batch around
+ * them, the grid or the pad bytes behind a message in d_src -- and
+ * gevws_deflate_raw_ctx produces the same bytes on the host.  41 024 bytes a
+ * connection: 672 MB of device memory for 16 384 connections.
+ *
+ * gevws_deflate_ctx_async is gevws_deflate_async plus d_msg_conn (one
+ * connection index per message), d_conn_ext (one byte per connection),
+ * d_def_ctx and n_conns.
+ *   - With any of the three pointers NULL it is gevws_deflate_async bit for
+ *     bit (which is that NULL call).
+ *   - A connection without GEVWS_EXT_SERVER_TAKEOVER is compressed as above;
+ *     its slot is neither read nor written.
+ *   - A takeover connection's message k gets the payload the compressor gives
+ *     for its bytes with the connection's earlier compressed messages --
+ *     earlier in this call's list and in earlier calls -- as history: a match
+ *     may reach back min(2^window_bits, 30 720) bytes across the message's
+ *     first byte.  The payload is still section 7.2.1's form: blocks with
+ *     BFINAL 0, then the empty stored block with its 00 00 ff ff taken off.
+ *     An empty message is the byte 00 and leaves the slot as it was.
+ *   - A peer that feeds payload + 00 00 ff ff of each message in order to one
+ *     raw inflater with a window of 2^window_bits gets the messages back.
+ *   - The messages of a takeover connection must stand next to each other in
+ *     the list, as one run of equal d_msg_conn: the wave of the run's first
+ *     message compresses the run in order, in both passes.  A takeover
+ *     connection that appears in two separate runs makes the call
+ *     GEVWS_ERR_INVALID on the device (every run but one counts once in
+ *     `errors`): two waves would race on one slot.
+ *   - GEVWS_DEFLATE_PLAIN_IF_NOT_SMALLER does not apply to a takeover
+ *     connection's messages: they always go out compressed, RSV1 set (a
+ *     message sent plain would have to stay out of the peer's window).
+ *     gevws_deflate_bound still holds, a run can always be a stored block.
+ *     The flag works as before for the other connections of the call.
+ *   - GEVWS_DEFLATE_DYNAMIC works with contexts: a run's tokens are the same,
+ *     only their coding differs.
+ *   - With d_prev a chain ends at the gated count: messages past it are not
+ *     compressed and do not enter the window.
+ *   - d_msg_conn[i] >= n_conns, or a malformed record (of any connection), is
+ *     GEVWS_ERR_INVALID: `errors` counts the records, nothing else is written,
+ *     no slot is written and none is indexed by such a record.
+ *   - GEVWS_ERR_CAPACITY writes nothing: the slots are untouched byte for
+ *     byte, so the retry sees the same contexts.
+ *   - With contexts max_msgs is at most 0x7FF00000 (the grid is rounded up to
+ *     a multiple of 1 024 workgroups). */
+#define GEVWS_EXT_SERVER_TAKEOVER 4u
+#define GEVWS_DEF_CTX_BYTES (64u + 32768u + 8192u)
+int gevws_deflate_ctx_async(gevws_ctx *ctx, void *stream,
+                            const gevws_deflate_msg *d_msgs, uint64_t max_msgs,
+                            const gevws_summary *d_prev /* may be NULL */,
+                            const uint8_t *d_src, uint64_t src_bytes, uint32_t flags,
+                            gevws_out_frame *d_out_frames, uint8_t *d_out, uint64_t out_cap,
+                            gevws_summary *d_summary, const uint32_t *d_msg_conn,
+                            const uint8_t *d_conn_ext, uint8_t *d_def_ctx, uint32_t n_conns);
+
+/* gevws_deflate_raw_flags over one slot in host memory
+ * (ctx[0, GEVWS_DEF_CTX_BYTES)): the message is compressed with the slot's
+ * window behind it and appended to the slot.  A zeroed slot gives
+ * gevws_deflate_raw_flags's bytes.  On GEVWS_ERR_CAPACITY out and the slot are
+ * untouched (*out_len = the need).  A NULL ctx is GEVWS_ERR_INVALID. */
+int gevws_deflate_raw_ctx(const uint8_t *in, uint64_t n, int window_bits, uint32_t flags,
+                          uint8_t *out, uint64_t cap, uint64_t *out_len, uint8_t *ctx);
+
+/* gevws_deflate_negotiate_flags for a server that may keep its own window
+ * too.  `flags` may hold GEVWS_NEGOTIATE_CLIENT_TAKEOVER and
+ * GEVWS_NEGOTIATE_SERVER_TAKEOVER; any other bit is GEVWS_ERR_INVALID.  With
+ * flags 0 or 1 it writes gevws_deflate_negotiate_flags's answer byte for
+ * byte.  With the server bit server_no_context_takeover is left out of the
+ * answer and GEVWS_EXT_SERVER_TAKEOVER is set in *conn_ext, unless the chosen
+ * offer carried the parameter: then it is echoed and the bit stays clear (RFC
+ * 7692 section 7.1.1.1).  server_max_window_bits is echoed as above: it is
+ * the window_bits the caller gives every message of that connection. */
+#define GEVWS_NEGOTIATE_SERVER_TAKEOVER 2u
+int gevws_deflate_negotiate_takeover(const uint8_t *offer, uint64_t n, uint32_t flags, uint8_t *out, uint64_t cap,
+                                     uint64_t *out_len, uint8_t *conn_ext);
+
 /* Measurement helper, not on the reference path: n bytes (n % 16 == 0, d_dst
  * 16-byte aligned, d_src any alignment) copied with the unmask kernel's
  * streaming access pattern minus the XOR and frame lookup -- the achievable
