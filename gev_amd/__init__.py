@@ -29,6 +29,8 @@ from ._abi import EXT_DEFLATE, INF_DONE, INF_PENDING, MSG_COMPRESSED, MSG_ERR_DE
 from ._abi import EXT_CLIENT_TAKEOVER, INF_CTX_BYTES, NEGOTIATE_CLIENT_TAKEOVER
 from ._abi import DEFLATE_DYNAMIC, DEFLATE_PLAIN_IF_NOT_SMALLER
 from ._abi import DEF_CTX_BYTES, EXT_SERVER_TAKEOVER, NEGOTIATE_SERVER_TAKEOVER
+from ._abi import BODY_INFLATED, BODY_JOINED, BODY_WHOLE, JOIN_ALL
+from ._abi import HANDLER_ECHO_BINARY, HANDLER_ECHO_TEXT, HANDLER_NONE
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
                    SUMMARY_UNORDERED, TILE, Header)
@@ -58,7 +60,10 @@ INFLATED_DTYPE = np.dtype([("out_off", "<u8"), ("length", "<u8"), ("status", "u1
                            ("reserved", "u1", (14,))])
 DEFLATE_MSG_DTYPE = np.dtype([("payload_off", "<u8"), ("length", "<u8"), ("opcode", "u1"), ("window_bits", "u1"),
                               ("reserved", "u1", (6,))])
+BODY_DTYPE = np.dtype([("off", "<u8"), ("length", "<u8"), ("conn", "<u4"), ("opcode", "u1"), ("flags", "u1"),
+                       ("status", "u1"), ("reserved", "u1", (9,))])
 assert FRAME_DTYPE.itemsize == 32 and CONN_OUT_DTYPE.itemsize == 32 and INFLATED_DTYPE.itemsize == 32
+assert BODY_DTYPE.itemsize == 32
 assert DEFLATE_MSG_DTYPE.itemsize == 24 and OUT_FRAME_DTYPE.itemsize == 32
 assert MSG_STATE_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 32 and CONN_MSG_DTYPE.itemsize == 32
 assert SUMMARY_DTYPE.itemsize == 64 and SYNTH_DTYPE.itemsize == 24
@@ -298,6 +303,47 @@ class Deflated:
         r = self.frames_host()[i]
         off, n = int(r["payload_off"]), int(r["payload_len"])
         return self.out[off: off + n].cpu().numpy().tobytes() if n else b""
+
+
+@dataclass
+class Bodies:
+    """Device-resident result of one join step (Engine.join)."""
+    bodies: "object"      # uint8 [n_messages, 32]   (gevws_body records)
+    out: "object"         # uint8 [out_cap + IN_PAD] (the inflated bytes below `base`, the joined bodies behind)
+    summary: "object"     # uint8 [64]               (gevws_summary)
+    payload: "object"     # the decode's payload arena (bodies that were left in place point into it)
+    n_messages: int
+    out_cap: int
+
+    def summary_host(self) -> np.ndarray:
+        return self.summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
+
+    def bodies_host(self) -> np.ndarray:
+        return self.bodies[: self.n_messages].cpu().numpy().reshape(-1).view(BODY_DTYPE)
+
+    def body_bytes(self, i: int) -> bytes:
+        """The bytes of message i, from the arena its record points into (b"" when not delivered)."""
+        r = self.bodies_host()[i]
+        off, n, fl = int(r["off"]), int(r["length"]), int(r["flags"])
+        if not fl & BODY_WHOLE or n == 0:
+            return b""
+        arena = self.out if fl & (BODY_JOINED | BODY_INFLATED) else self.payload
+        return arena[off: off + n].cpu().numpy().tobytes()
+
+
+@dataclass
+class Echo:
+    """What Engine.echo_messages sends: the compressed replies' wire bytes and
+    the plain replies' (device tensors), each with its per-reply connection and
+    wire offset (numpy), and reply_of[m] = message m's index in its list or -1."""
+    def_wire: "object"
+    def_conn: np.ndarray
+    def_off: np.ndarray
+    plain_wire: "object"
+    plain_conn: np.ndarray
+    plain_off: np.ndarray
+    reply_of: np.ndarray
+    deflated: Optional["Deflated"] = None   # the deflate step's records and payloads
 
 
 class _DevAddr:
@@ -761,6 +807,145 @@ class Engine:
                 raise RuntimeError(f"deflate: {status_string(int(s['status']))}")
             return res
         raise RuntimeError("deflate: capacity retry failed")
+
+    # -------------------------------------------------------------- join / reply
+    def join_async(self, frames, max_frames: int, messages, max_messages: int, msg_of, msg_summary, payload, inflated,
+                   inflate_summary, flags: int, bodies, out, out_cap: int, summary, stream=None) -> None:
+        """gevws_join_async on device tensors: one contiguous body per whole
+        message of a message pass; fragmented ones are gathered into `out`
+        behind the inflate's bytes (inflated / inflate_summary: the inflate
+        step's records and summary, or None)."""
+        st = lib.gevws_join_async(
+            self._ctx, _stream_handle(stream), frames.data_ptr(), max_frames, messages.data_ptr(), max_messages,
+            msg_of.data_ptr(), msg_summary.data_ptr(), payload.data_ptr(),
+            inflated.data_ptr() if inflated is not None else None,
+            inflate_summary.data_ptr() if inflate_summary is not None else None, flags, bodies.data_ptr(),
+            out.data_ptr(), out_cap, summary.data_ptr())
+        if st != OK:
+            raise RuntimeError(f"gevws_join_async: {status_string(st)}")
+
+    def join(self, out: "Batch", msgs: "Messages", inflated: Optional["Inflated"] = None, flags: int = 0,
+             out_cap: Optional[int] = None, stream=None) -> "Bodies":
+        """The join step behind Engine.messages (and Engine.inflate): every
+        whole message's bytes as one (off, length).  With `inflated` the
+        inflated bytes are kept below `base` of the returned arena and the
+        joined bodies follow them.  Grows the arena once on ERR_CAPACITY
+        (nothing is written by the call that did not fit)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        n = int(msgs.summary_host()["frames"])
+        inf_bytes = int(inflated.summary_host()["payload_bytes"]) if inflated is not None else 0
+        if out_cap is None:  # a joined body never takes more than its frames' slots
+            out_cap = (inf_bytes + 15) // 16 * 16 + int(out.summary_host()["payload_bytes"])
+        for attempt in range(2):
+            arena = torch.empty(max(out_cap, 16) + IN_PAD, dtype=torch.uint8, device=dev)
+            if inf_bytes and inf_bytes <= out_cap:  # (a smaller out_cap fails with the need, and the retry copies)
+                arena[:inf_bytes] = inflated.out[:inf_bytes]
+            res = Bodies(bodies=torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=dev), out=arena,
+                         summary=torch.zeros(64, dtype=torch.uint8, device=dev), payload=out.payload, n_messages=n,
+                         out_cap=out_cap)
+            self.join_async(out.frames, msgs.n_frames, msgs.messages, n, msgs.msg_of, msgs.summary, out.payload,
+                            inflated.inflated if inflated is not None else None,
+                            inflated.summary if inflated is not None else None, flags, res.bodies, arena, out_cap,
+                            res.summary, stream)
+            torch.cuda.synchronize(self.device)
+            s = res.summary_host()
+            if int(s["status"]) == ERR_CAPACITY and attempt == 0:
+                out_cap = int(s["payload_bytes"])
+                continue
+            if int(s["status"]) != OK:
+                raise RuntimeError(f"join: {status_string(int(s['status']))}")
+            return res
+        raise RuntimeError("join: capacity retry failed")
+
+    def reply_bodies_async(self, bodies, max_messages: int, msg_summary, join_summary, policy: int, conn_ext,
+                           window_bits, n_conns: int, def_msgs, def_conn, def_summary, plain, plain_conn,
+                           plain_summary, reply_of, stream=None) -> None:
+        """gevws_reply_bodies_async on device tensors: the delivered bodies as
+        the deflate step's message list (connections with EXT_DEFLATE in
+        conn_ext) and the encoder's frame list (the others)."""
+        st = lib.gevws_reply_bodies_async(
+            self._ctx, _stream_handle(stream), bodies.data_ptr(), max_messages, msg_summary.data_ptr(),
+            join_summary.data_ptr(), policy, conn_ext.data_ptr() if conn_ext is not None else None,
+            window_bits.data_ptr() if window_bits is not None else None, n_conns, def_msgs.data_ptr(),
+            def_conn.data_ptr(), def_summary.data_ptr(), plain.data_ptr(), plain_conn.data_ptr(),
+            plain_summary.data_ptr(), reply_of.data_ptr())
+        if st != OK:
+            raise RuntimeError(f"gevws_reply_bodies_async: {status_string(st)}")
+
+    def encode_replies_async(self, replies, max_replies: int, dispatched, payload, out, out_cap: int, out_off,
+                             summary, stream=None) -> None:
+        """gevws_encode_replies_async: encode_async with the count read on the
+        device from the producing step's summary."""
+        st = lib.gevws_encode_replies_async(self._ctx, _stream_handle(stream), replies.data_ptr(), max_replies,
+                                            dispatched.data_ptr(), payload.data_ptr(), out.data_ptr(), out_cap,
+                                            out_off.data_ptr(), summary.data_ptr())
+        if st != OK:
+            raise RuntimeError(f"gevws_encode_replies_async: {status_string(st)}")
+
+    def echo_messages(self, out: "Batch", msgs: "Messages", bodies: "Bodies", policy: int, conn_ext,
+                      window_bits=None, contexts=None, flags: int = 0, stream=None) -> "Echo":
+        """A message-level echo with the lists built on the device: reply ->
+        deflate (with contexts: deflate_ctx) -> the two encodes, all on
+        `bodies.out`.  conn_ext / window_bits: uint8 [n_conns] device tensors
+        (or None), contexts: uint8 [n_conns, DEF_CTX_BYTES] for connections with
+        EXT_SERVER_TAKEOVER, flags: the deflate step's.  The bodies come from a
+        join with JOIN_ALL."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        n, n_conns = bodies.n_messages, out.n_conns
+        cap = max(n, 1)
+        z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        def_msgs, def_conn, def_sum = z(cap, 24), z(cap, dt=torch.int32), z(64)
+        plain, plain_conn, plain_sum = z(cap, 32), z(cap, dt=torch.int32), z(64)
+        reply_of = torch.full((cap,), -1, dtype=torch.int64, device=dev)
+        empty = Echo(z(0), np.zeros(0, np.uint32), np.zeros(0, np.uint64), z(0), np.zeros(0, np.uint32),
+                     np.zeros(0, np.uint64), np.zeros(0, np.int64))
+        if n == 0:
+            return empty
+        self.reply_bodies_async(bodies.bodies, n, msgs.summary, bodies.summary, policy, conn_ext, window_bits, n_conns,
+                                def_msgs, def_conn, def_sum, plain, plain_conn, plain_sum, reply_of, stream)
+        torch.cuda.synchronize(self.device)
+        ds = def_sum.cpu().numpy().view(SUMMARY_DTYPE)[0]
+        ps = plain_sum.cpu().numpy().view(SUMMARY_DTYPE)[0]
+        if int(ds["status"]) != OK or int(ps["status"]) != OK:
+            raise RuntimeError(f"reply_bodies: {status_string(int(ds['status']))} ({int(ds['errors'])} records)")
+        nd, npl = int(ds["frames"]), int(ps["frames"])
+        src_bytes = int(bodies.summary_host()["payload_bytes"])
+        # the deflate step: gevws_deflate_bound per message holds whatever the bytes are
+        dm = def_msgs[:nd].cpu().numpy().reshape(-1).view(DEFLATE_MSG_DTYPE)
+        dcap = int(sum((deflate_bound(int(x)) + 15) // 16 * 16 for x in dm["length"])) + 16
+        res = Deflated(frames=z(cap, 32), out=torch.empty(dcap + _abi.OUT_PAD, dtype=torch.uint8, device=dev),
+                       summary=z(64), n_messages=nd)
+        if contexts is not None and conn_ext is not None:
+            self.deflate_ctx_async(def_msgs, n, def_sum, bodies.out, src_bytes, flags, res.frames, res.out, dcap,
+                                   res.summary, def_conn, conn_ext, contexts, int(contexts.shape[0]), stream)
+        else:
+            self.deflate_async(def_msgs, n, def_sum, bodies.out, src_bytes, flags, res.frames, res.out, dcap,
+                               res.summary, stream)
+        torch.cuda.synchronize(self.device)
+        s = res.summary_host()
+        if int(s["status"]) != OK:
+            raise RuntimeError(f"echo_messages: deflate: {status_string(int(s['status']))}")
+        wires = []
+        for recs, gate, payload, total in (
+                (res.frames, res.summary, res.out, int(s["payload_len"])),
+                (plain, plain_sum, bodies.out,
+                 int(plain[:npl].cpu().numpy().reshape(-1).view(OUT_FRAME_DTYPE)["payload_len"].sum()))):
+            k = int(gate.cpu().numpy().view(SUMMARY_DTYPE)[0]["frames"])
+            wcap = total + 14 * k + 16
+            wire = torch.empty(wcap + _abi.OUT_PAD, dtype=torch.uint8, device=dev)
+            off = torch.zeros(cap, dtype=torch.int64, device=dev)
+            esum = z(64)
+            self.encode_replies_async(recs, n, gate, payload, wire, wcap, off, esum, stream)
+            torch.cuda.synchronize(self.device)
+            es = esum.cpu().numpy().view(SUMMARY_DTYPE)[0]
+            if int(es["status"]) != OK:
+                raise RuntimeError(f"echo_messages: encode: {status_string(int(es['status']))}")
+            wires.append((wire[: int(es["payload_bytes"])], off[:k].cpu().numpy().astype(np.uint64)))
+        return Echo(def_wire=wires[0][0], def_conn=def_conn[:nd].cpu().numpy().view(np.uint32), def_off=wires[0][1],
+                    plain_wire=wires[1][0], plain_conn=plain_conn[:npl].cpu().numpy().view(np.uint32),
+                    plain_off=wires[1][1], reply_of=reply_of[:n].cpu().numpy(), deflated=res)
 
     def messages(self, out: "Batch", state=None, max_messages: Optional[int] = None, stream=None, *,
                  conn_ext=None) -> "Messages":

@@ -78,6 +78,11 @@ DEF_CTX_BYTES = 64 + 32768 + 8192  # one connection's slot of d_def_ctx
 NEGOTIATE_SERVER_TAKEOVER = 2  # gevws_deflate_negotiate_takeover flag
 INF_DONE = 1
 INF_PENDING = 2
+# the join step (gevws_join_async): call flag and body flags
+JOIN_ALL = 1
+BODY_WHOLE = 1
+BODY_JOINED = 2
+BODY_INFLATED = 4
 
 IN_PAD = 64
 MEM_DEFAULT, MEM_FINE, MEM_UNCACHED = 0, 1, 2  # gevws_device_alloc kinds
@@ -175,6 +180,13 @@ class Inflated(ctypes.Structure):
                 ("flags", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 14)]
 
 
+class Body(ctypes.Structure):
+    """gevws_body: where one message's contiguous bytes are (the join step)."""
+    _fields_ = [("off", ctypes.c_uint64), ("length", ctypes.c_uint64), ("conn", ctypes.c_uint32),
+                ("opcode", ctypes.c_uint8), ("flags", ctypes.c_uint8), ("status", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 9)]
+
+
 class Reject(ctypes.Structure):
     """gevws_reject: RejectConnectionError options (ws/errors.go:81-129)."""
     _fields_ = [("code", ctypes.c_int32), ("plain", ctypes.c_int32), ("reason", ctypes.c_void_p),
@@ -220,7 +232,7 @@ assert ctypes.sizeof(Header) == 16 and ctypes.sizeof(Frame) == 32
 assert ctypes.sizeof(ConnIn) == 16 and ctypes.sizeof(ConnOut) == 32
 assert ctypes.sizeof(Summary) == 64 and ctypes.sizeof(SynthDesc) == 24
 assert ctypes.sizeof(MsgState) == 8 and ctypes.sizeof(Message) == 32 and ctypes.sizeof(ConnMsg) == 32
-assert ctypes.sizeof(Inflated) == 32
+assert ctypes.sizeof(Inflated) == 32 and ctypes.sizeof(Body) == 32
 
 P = ctypes.c_void_p
 U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -294,6 +306,10 @@ SIGNATURES = {
                                              ctypes.POINTER(ctypes.c_uint64), P]),
     "gevws_deflate_negotiate_takeover": (ctypes.c_int, [P, ctypes.c_uint64, ctypes.c_uint32, P, ctypes.c_uint64,
                                                         ctypes.POINTER(ctypes.c_uint64), P]),
+    "gevws_join_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, P, P, P, P, P, ctypes.c_uint32,
+                                        P, P, ctypes.c_uint64, P]),
+    "gevws_reply_bodies_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, ctypes.c_int, P, P, ctypes.c_uint32,
+                                                P, P, P, P, P, P, P]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),
     "gevws_synth_async": (ctypes.c_int, [P, P, P, P, ctypes.c_uint64, ctypes.c_uint64]),
     "gevws_synth_verify_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P,

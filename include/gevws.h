@@ -440,7 +440,8 @@ typedef struct gevws_msg_state {
 
 /* One message: the data frames (opcode 1 / 2 and its continuations) from
  * first_frame on that map to it in d_msg_of.  A single-frame message's payload
- * is its frame's; a fragmented one's stays in its frames' slots. */
+ * is its frame's; a fragmented one's stays in its frames' slots
+ * (gevws_join_async below gathers it into one contiguous body). */
 typedef struct gevws_message {
     uint64_t first_frame;   /* record index of its first data frame in this batch */
     uint64_t length;        /* payload bytes of its data frames in this batch */
@@ -898,6 +899,119 @@ int gevws_deflate_raw_ctx(const uint8_t *in, uint64_t n, int window_bits, uint32
 #define GEVWS_NEGOTIATE_SERVER_TAKEOVER 2u
 int gevws_deflate_negotiate_takeover(const uint8_t *offer, uint64_t n, uint32_t flags, uint8_t *out, uint64_t cap,
                                      uint64_t *out_len, uint8_t *conn_ext);
+
+/* The join step and the reply step: one contiguous body per whole message,
+ * and the bodies turned into the deflate step's message list and the
+ * encoder's frame list on the device, so that decode -> messages -> inflate ->
+ * join -> reply -> deflate -> encode is one stream-ordered chain.  Additions
+ * to ABI version 3: nothing above changes.
+ *
+ * gevws_join_async stands behind the message pass (and, where there is one,
+ * the inflate step) and works on their tables; d_bodies[m] belongs to
+ * d_messages[m].
+ *
+ * Delivered.  A message is delivered (GEVWS_BODY_WHOLE) when it has both
+ * GEVWS_MSG_BEGIN and GEVWS_MSG_END, its status is GEVWS_MSG_OK and, if it is
+ * GEVWS_MSG_COMPRESSED, d_inflated is given and d_inflated[m] has
+ * GEVWS_INF_DONE with status GEVWS_MSG_OK.  Every other message -- one still
+ * open or continued from the carry state, a UTF-8 failure, a failed or
+ * pending inflate, a compressed message with d_inflated == NULL -- gets flags
+ * 0, off = length = 0 and its status copied (a compressed message's is the
+ * inflate record's when d_inflated is given), and takes no space.
+ *
+ * Where the bytes are.  A delivered compressed message gets
+ * GEVWS_BODY_INFLATED: off / length are the inflate record's and nothing is
+ * copied.  A delivered plain message with nframes >= 2 is copied
+ * (GEVWS_BODY_JOINED); with GEVWS_JOIN_ALL in `flags` every delivered plain
+ * message is.  Any other delivered message stays where it is: off is its one
+ * frame's payload_off in d_payload.
+ *
+ * What is copied.  The first hdr.length bytes of each of the message's data
+ * frames in order -- the frames f from first_frame on with d_msg_of[f] == m;
+ * control frames in between, empty fragments and the slots' padding are
+ * skipped.  Source bytes are read as whole aligned 16-byte vectors, and only
+ * vectors that hold at least one counted byte: the arena's last vector may be
+ * a fragment's last.  d_payload and d_out start on a 16-byte boundary.
+ *
+ * Where it lands.  The copied bodies lie in d_out in message order, each on a
+ * GEVWS_PAYLOAD_ALIGN boundary, the pad behind each zeroed; a zero-length body
+ * takes no space (its off is where the next one starts).  They start at
+ * `base`: d_inflate_summary->payload_bytes rounded up to 16 when that summary
+ * is given, else 0.  out_cap is the capacity of the whole of d_out, the
+ * inflate's part included: in the chained use d_out is the inflate's own
+ * buffer, and no byte below `base` is written.  Every store is a whole vector
+ * inside [base, payload_bytes).
+ *
+ * d_summary: frames = delivered bodies, payload_bytes = base + the bytes the
+ * copied bodies take (the new end of d_out), payload_len = the sum of the
+ * delivered lengths, errors 0; status GEVWS_ERR_CAPACITY when payload_bytes >
+ * out_cap -- payload_bytes then holds the need and neither d_bodies nor d_out
+ * is written, so the caller retries.  A failed d_msg_summary, no messages, or
+ * a given d_inflate_summary whose status is not GEVWS_OK give a zero summary
+ * and read none of the inputs.  Any flag bit but GEVWS_JOIN_ALL is
+ * GEVWS_ERR_INVALID from the call; max_frames is at most 2^32 - 1.
+ * Out of scope: a message that spans two passes stays undelivered, as it
+ * stays GEVWS_INF_PENDING in the inflate. */
+#define GEVWS_JOIN_ALL 1u          /* call flag: copy single-frame plain messages too */
+#define GEVWS_BODY_WHOLE    1u     /* delivered: off / length are valid */
+#define GEVWS_BODY_JOINED   2u     /* its bytes were written to d_out by this call */
+#define GEVWS_BODY_INFLATED 4u     /* its bytes are the inflate step's, already in d_out */
+typedef struct gevws_body {        /* 32 bytes; d_bodies[m] belongs to d_messages[m] */
+    uint64_t off;      /* into d_out if JOINED or INFLATED, else into d_payload; on GEVWS_PAYLOAD_ALIGN */
+    uint64_t length;
+    uint32_t conn;
+    uint8_t opcode;    /* 1 / 2, the message's */
+    uint8_t flags;     /* GEVWS_BODY_*; 0 = not delivered (off = length = 0) */
+    uint8_t status;    /* the message's status; for a compressed message the inflate's */
+    uint8_t reserved[9];
+} gevws_body;
+int gevws_join_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_frames, uint64_t max_frames,
+                     const gevws_message *d_messages, uint64_t max_messages, const int64_t *d_msg_of,
+                     const gevws_summary *d_msg_summary, const uint8_t *d_payload,
+                     const gevws_inflated *d_inflated /* may be NULL */,
+                     const gevws_summary *d_inflate_summary /* may be NULL */, uint32_t flags,
+                     gevws_body *d_bodies, uint8_t *d_out, uint64_t out_cap, gevws_summary *d_summary);
+
+/* gevws_reply_bodies_async is the message-level stand-in for the user's
+ * handler, as gevws_dispatch_async's policy is at frame level: with
+ * GEVWS_HANDLER_ECHO_BINARY (opcode 2) or GEVWS_HANDLER_ECHO_TEXT (opcode 1)
+ * every delivered body gets one reply, in message order -- an empty message
+ * too (compressed, it is the byte 00); GEVWS_HANDLER_NONE gives no replies and
+ * looks at no record; any other policy is GEVWS_ERR_INVALID from the call.
+ *
+ * The bodies are the first min(d_msg_summary->frames, max_messages) records;
+ * a failed d_msg_summary or d_join_summary gives two zero summaries and
+ * writes nothing else.
+ *   - The deflate list, for connections whose d_conn_ext byte has
+ *     GEVWS_EXT_DEFLATE: d_def_msgs[k] = {body.off, body.length, opcode, the
+ *     connection's d_conn_window_bits byte (0 when that is NULL; passed through
+ *     unchecked, the deflate step rejects a bad one)}, d_def_conn[k] = the
+ *     connection.  d_def_summary->frames is the count: the summary is the
+ *     d_prev of gevws_deflate_ctx_async, with the join's d_out as d_src.  The
+ *     list keeps the message order, which is by connection, so a connection's
+ *     messages form one run of equal d_def_conn, as takeover requires.
+ *   - The plain list, for every other connection (d_conn_ext == NULL: all):
+ *     d_plain[k] = {hdr = {fin 1, rsv 0, opcode, masked 0, mask 0, length},
+ *     payload_off = body.off, payload_len = length}, d_plain_conn[k] = the
+ *     connection.  d_plain_summary->frames is the count: the summary is the
+ *     d_dispatched of gevws_encode_replies_async, with the join's d_out as
+ *     d_payload.
+ *   - d_reply_of[m], for each of the bodies, = the index in its connection's
+ *     list, or -1.
+ *   - The two summaries' other fields are zero.  All five arrays hold
+ *     max_messages entries.
+ *   - Both lists address one arena, so a delivered body with neither
+ *     GEVWS_BODY_JOINED nor GEVWS_BODY_INFLATED (a join without
+ *     GEVWS_JOIN_ALL) is malformed, and so is conn >= n_conns: both summaries
+ *     then get GEVWS_ERR_INVALID with `errors` counting such records, the
+ *     other fields zero, and nothing else is written. */
+int gevws_reply_bodies_async(gevws_ctx *ctx, void *stream, const gevws_body *d_bodies, uint64_t max_messages,
+                             const gevws_summary *d_msg_summary, const gevws_summary *d_join_summary, int policy,
+                             const uint8_t *d_conn_ext /* may be NULL */,
+                             const uint8_t *d_conn_window_bits /* may be NULL: 0 */, uint32_t n_conns,
+                             gevws_deflate_msg *d_def_msgs, uint32_t *d_def_conn, gevws_summary *d_def_summary,
+                             gevws_out_frame *d_plain, uint32_t *d_plain_conn, gevws_summary *d_plain_summary,
+                             int64_t *d_reply_of);
 
 /* Measurement helper, not on the reference path: n bytes (n % 16 == 0, d_dst
  * 16-byte aligned, d_src any alignment) copied with the unmask kernel's
