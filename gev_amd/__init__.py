@@ -30,6 +30,7 @@ from ._abi import EXT_CLIENT_TAKEOVER, INF_CTX_BYTES, NEGOTIATE_CLIENT_TAKEOVER
 from ._abi import DEFLATE_DYNAMIC, DEFLATE_PLAIN_IF_NOT_SMALLER
 from ._abi import DEF_CTX_BYTES, EXT_SERVER_TAKEOVER, NEGOTIATE_SERVER_TAKEOVER
 from ._abi import BODY_INFLATED, BODY_JOINED, BODY_WHOLE, JOIN_ALL
+from ._abi import CARRY_LOST, CARRY_OPEN
 from ._abi import HANDLER_ECHO_BINARY, HANDLER_ECHO_TEXT, HANDLER_NONE
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
@@ -63,7 +64,9 @@ DEFLATE_MSG_DTYPE = np.dtype([("payload_off", "<u8"), ("length", "<u8"), ("opcod
 BODY_DTYPE = np.dtype([("off", "<u8"), ("length", "<u8"), ("conn", "<u4"), ("opcode", "u1"), ("flags", "u1"),
                        ("status", "u1"), ("reserved", "u1", (9,))])
 assert FRAME_DTYPE.itemsize == 32 and CONN_OUT_DTYPE.itemsize == 32 and INFLATED_DTYPE.itemsize == 32
-assert BODY_DTYPE.itemsize == 32
+CARRY_DTYPE = np.dtype([("off", "<u8"), ("length", "<u8"), ("opcode", "u1"), ("flags", "u1"), ("status", "u1"),
+                        ("reserved", "u1", (13,))])
+assert BODY_DTYPE.itemsize == 32 and CARRY_DTYPE.itemsize == 32
 assert DEFLATE_MSG_DTYPE.itemsize == 24 and OUT_FRAME_DTYPE.itemsize == 32
 assert MSG_STATE_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 32 and CONN_MSG_DTYPE.itemsize == 32
 assert SUMMARY_DTYPE.itemsize == 64 and SYNTH_DTYPE.itemsize == 24
@@ -314,9 +317,13 @@ class Bodies:
     payload: "object"     # the decode's payload arena (bodies that were left in place point into it)
     n_messages: int
     out_cap: int
+    carry_summary: "object" = None   # uint8 [64], a join with a carry: the carry side's gevws_summary
 
     def summary_host(self) -> np.ndarray:
         return self.summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
+
+    def carry_summary_host(self) -> Optional[np.ndarray]:
+        return None if self.carry_summary is None else self.carry_summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
 
     def bodies_host(self) -> np.ndarray:
         return self.bodies[: self.n_messages].cpu().numpy().reshape(-1).view(BODY_DTYPE)
@@ -329,6 +336,48 @@ class Bodies:
             return b""
         arena = self.out if fl & (BODY_JOINED | BODY_INFLATED) else self.payload
         return arena[off: off + n].cpu().numpy().tobytes()
+
+
+class Carry:
+    """The join step's carry between passes (Engine.join(carry=...)): every
+    connection's open plain message, its record and its bytes so far, on the
+    device.  Two sides that Engine.join swaps after each pass that succeeded:
+    `records` / `arena` hold the state behind the last pass."""
+
+    def __init__(self, engine: "Engine", n_conns: int, max_message_bytes: int, arena_bytes: int = 0):
+        torch = _torch()
+        self.device = torch.device("cuda", engine.device)
+        self.n_conns, self.max_message_bytes = n_conns, max_message_bytes
+        self.records = [torch.zeros((max(n_conns, 1), 32), dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self.arenas = [self._arena(arena_bytes) for _ in range(2)]
+        self.used = 0     # bytes of `arena` the records point into
+        self.side = 0     # the side the next pass reads
+
+    def _arena(self, nbytes: int):
+        torch = _torch()
+        return torch.zeros((max(nbytes, 0) + 15) // 16 * 16 + IN_PAD, dtype=torch.uint8, device=self.device)
+
+    @property
+    def records_in(self):
+        return self.records[self.side]
+
+    @property
+    def arena(self):
+        return self.arenas[self.side]
+
+    def cap(self, side: int) -> int:
+        return int(self.arenas[side].numel()) - IN_PAD
+
+    def records_host(self) -> np.ndarray:
+        return self.records_in[: self.n_conns].cpu().numpy().reshape(-1).view(CARRY_DTYPE)
+
+    def carried_bytes(self, c: int) -> bytes:
+        """The bytes kept of connection c's open message (b"" when none are)."""
+        r = self.records_host()[c]
+        off, n = int(r["off"]), int(r["length"])
+        if not int(r["flags"]) & CARRY_OPEN or n == 0:
+            return b""
+        return self.arena[off: off + n].cpu().numpy().tobytes()
 
 
 @dataclass
@@ -824,13 +873,77 @@ class Engine:
         if st != OK:
             raise RuntimeError(f"gevws_join_async: {status_string(st)}")
 
+    def join_carry_async(self, frames, max_frames: int, messages, max_messages: int, msg_of, msg_summary, payload,
+                         inflated, inflate_summary, flags: int, bodies, out, out_cap: int, summary, conn_msg,
+                         n_conns: int, max_message_bytes: int, carry_in, carry_src, carry_src_bytes: int, carry_out,
+                         carry_dst, carry_cap: int, carry_summary, stream=None) -> None:
+        """gevws_join_carry_async on device tensors: join_async plus the carry
+        of open plain messages from pass to pass (carry_in / carry_src: the
+        previous pass's carry_out / carry_dst, or None).  With conn_msg,
+        carry_out, carry_dst or carry_summary None it is join_async."""
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        st = lib.gevws_join_carry_async(
+            self._ctx, _stream_handle(stream), p(frames), max_frames, p(messages), max_messages, p(msg_of),
+            p(msg_summary), p(payload), p(inflated), p(inflate_summary), flags, p(bodies), p(out), out_cap,
+            p(summary), p(conn_msg), n_conns, max_message_bytes, p(carry_in), p(carry_src), carry_src_bytes,
+            p(carry_out), p(carry_dst), carry_cap, p(carry_summary))
+        if st != OK:
+            raise RuntimeError(f"gevws_join_carry_async: {status_string(st)}")
+
+    def _join_with_carry(self, out: "Batch", msgs: "Messages", inflated, flags: int, out_cap: Optional[int], stream,
+                         conn_msg, carry: "Carry") -> "Bodies":
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        n = int(msgs.summary_host()["frames"])
+        inf_bytes = int(inflated.summary_host()["payload_bytes"]) if inflated is not None else 0
+        if out_cap is None:  # the frames' slots, and a continued message's carried bytes in front
+            out_cap = (inf_bytes + 15) // 16 * 16 + int(out.summary_host()["payload_bytes"]) + carry.used + 16
+        src, dst = carry.side, 1 - carry.side
+        need = carry.used + int(out.summary_host()["payload_bytes"])  # every byte kept or carried on
+        if carry.cap(dst) < need:
+            carry.arenas[dst] = carry._arena(need)
+        for attempt in range(2):
+            arena = torch.empty(max(out_cap, 16) + IN_PAD, dtype=torch.uint8, device=dev)
+            if inf_bytes and inf_bytes <= out_cap:
+                arena[:inf_bytes] = inflated.out[:inf_bytes]
+            res = Bodies(bodies=torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=dev), out=arena,
+                         summary=torch.zeros(64, dtype=torch.uint8, device=dev), payload=out.payload, n_messages=n,
+                         out_cap=out_cap, carry_summary=torch.zeros(64, dtype=torch.uint8, device=dev))
+            self.join_carry_async(out.frames, msgs.n_frames, msgs.messages, n, msgs.msg_of, msgs.summary, out.payload,
+                                  inflated.inflated if inflated is not None else None,
+                                  inflated.summary if inflated is not None else None, flags, res.bodies, arena,
+                                  out_cap, res.summary, conn_msg, carry.n_conns, carry.max_message_bytes,
+                                  carry.records[src], carry.arenas[src], carry.used, carry.records[dst],
+                                  carry.arenas[dst], carry.cap(dst), res.carry_summary, stream)
+            torch.cuda.synchronize(self.device)
+            s, cs = res.summary_host(), res.carry_summary_host()
+            short = [x for x in (s, cs) if int(x["status"]) == ERR_CAPACITY]
+            if short and attempt == 0:  # neither side was written: grow what did not fit, same inputs again
+                if int(s["status"]) == ERR_CAPACITY:
+                    out_cap = int(s["payload_bytes"])
+                if int(cs["status"]) == ERR_CAPACITY:
+                    carry.arenas[dst] = carry._arena(int(cs["payload_bytes"]))
+                continue
+            for x in (s, cs):
+                if int(x["status"]) != OK:
+                    raise RuntimeError(f"join: {status_string(int(x['status']))}")
+            carry.side, carry.used = dst, int(cs["payload_bytes"])  # (only now: a failed call keeps the old carry)
+            return res
+        raise RuntimeError("join: capacity retry failed")
+
     def join(self, out: "Batch", msgs: "Messages", inflated: Optional["Inflated"] = None, flags: int = 0,
-             out_cap: Optional[int] = None, stream=None) -> "Bodies":
+             out_cap: Optional[int] = None, stream=None, *, conn_msg=None, carry: Optional["Carry"] = None) -> "Bodies":
         """The join step behind Engine.messages (and Engine.inflate): every
         whole message's bytes as one (off, length).  With `inflated` the
         inflated bytes are kept below `base` of the returned arena and the
         joined bodies follow them.  Grows the arena once on ERR_CAPACITY
-        (nothing is written by the call that did not fit)."""
+        (nothing is written by the call that did not fit).  With `carry` (a
+        Carry; conn_msg: the message pass's table, msgs.conn_msg by default) a
+        plain message that spans passes is kept in the carry and delivered with
+        its FIN frame; the carry's sides are swapped after a call that succeeded."""
+        if carry is not None:
+            return self._join_with_carry(out, msgs, inflated, flags, out_cap, stream,
+                                         msgs.conn_msg if conn_msg is None else conn_msg, carry)
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n = int(msgs.summary_host()["frames"])
@@ -1587,4 +1700,4 @@ __all__ = ["Engine", "Batch", "Comm", "RingBuffer", "Connection", "Protocol", "H
            "ERR_NOT_UPGRADED", "IN_PAD", "PAYLOAD_ALIGN", "TILE", "SUMMARY_UNORDERED",
            "DEFLATE_MSG_DTYPE", "DEFLATE_PLAIN_IF_NOT_SMALLER", "DEFLATE_DYNAMIC", "Deflated", "deflate_raw", "deflate_bound",
            "deflate_raw_ctx", "deflate_negotiate_takeover", "DEF_CTX_BYTES", "EXT_SERVER_TAKEOVER",
-           "NEGOTIATE_SERVER_TAKEOVER"]
+           "NEGOTIATE_SERVER_TAKEOVER", "Carry", "CARRY_DTYPE", "CARRY_OPEN", "CARRY_LOST"]

@@ -83,6 +83,9 @@ JOIN_ALL = 1
 BODY_WHOLE = 1
 BODY_JOINED = 2
 BODY_INFLATED = 4
+# the join's carry (gevws_join_carry_async): gevws_carry.flags
+CARRY_OPEN = 1
+CARRY_LOST = 2
 
 IN_PAD = 64
 MEM_DEFAULT, MEM_FINE, MEM_UNCACHED = 0, 1, 2  # gevws_device_alloc kinds
@@ -187,6 +190,12 @@ class Body(ctypes.Structure):
                 ("reserved", ctypes.c_uint8 * 9)]
 
 
+class Carry(ctypes.Structure):
+    """gevws_carry: one connection's open plain message between passes (gevws_join_carry_async)."""
+    _fields_ = [("off", ctypes.c_uint64), ("length", ctypes.c_uint64), ("opcode", ctypes.c_uint8),
+                ("flags", ctypes.c_uint8), ("status", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 13)]
+
+
 class Reject(ctypes.Structure):
     """gevws_reject: RejectConnectionError options (ws/errors.go:81-129)."""
     _fields_ = [("code", ctypes.c_int32), ("plain", ctypes.c_int32), ("reason", ctypes.c_void_p),
@@ -232,7 +241,7 @@ assert ctypes.sizeof(Header) == 16 and ctypes.sizeof(Frame) == 32
 assert ctypes.sizeof(ConnIn) == 16 and ctypes.sizeof(ConnOut) == 32
 assert ctypes.sizeof(Summary) == 64 and ctypes.sizeof(SynthDesc) == 24
 assert ctypes.sizeof(MsgState) == 8 and ctypes.sizeof(Message) == 32 and ctypes.sizeof(ConnMsg) == 32
-assert ctypes.sizeof(Inflated) == 32 and ctypes.sizeof(Body) == 32
+assert ctypes.sizeof(Inflated) == 32 and ctypes.sizeof(Body) == 32 and ctypes.sizeof(Carry) == 32
 
 P = ctypes.c_void_p
 U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -308,6 +317,9 @@ SIGNATURES = {
                                                         ctypes.POINTER(ctypes.c_uint64), P]),
     "gevws_join_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, P, P, P, P, P, ctypes.c_uint32,
                                         P, P, ctypes.c_uint64, P]),
+    "gevws_join_carry_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, P, P, P, P, P,
+                                              ctypes.c_uint32, P, P, ctypes.c_uint64, P, P, ctypes.c_uint32,
+                                              ctypes.c_uint64, P, P, ctypes.c_uint64, P, P, ctypes.c_uint64, P]),
     "gevws_reply_bodies_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, ctypes.c_int, P, P, ctypes.c_uint32,
                                                 P, P, P, P, P, P, P]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),

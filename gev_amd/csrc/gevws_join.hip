@@ -20,6 +20,14 @@
 // Only k_join_copy touches payload bytes: L read, L rounded up to 16 written a
 // copied body.
 //
+// The carry (gevws_join_carry_async): the same four launches once more over
+// the connections instead of the messages -- k_carry_size / k_scan_blocks /
+// k_carry_place, then k_join_copy over the carry's tables into d_carry_dst --
+// and k_carry_verdict between the scans and the place passes.  The kernels of
+// the body side are templates on CARRY: <false> is the code of the NULL call,
+// <true> gives a continued message the connection's carried bytes as one more
+// fragment in front of its first frame.
+//
 // The reply step: k_reply_count / k_scan_blocks / k_reply_verdict /
 // k_reply_emit, an order-preserving compaction of the delivered bodies into the
 // two lists (fields 0 and 1 of the block partials are the two lists' counts).
@@ -43,6 +51,11 @@ constexpr int kJoinRounds = 4;    // fragments of one tile a wave takes as whole
 constexpr uint64_t kJoinRowBytes = 1024;  // ... while they are at least this long; shorter ones lane by lane
 
 // ------------------------------------------------------------------ scratch
+// What a copied body has beside its frames: the first `pre` bytes come from
+// carry_src[psrc, psrc + pre); its frames are those of message `msg`.
+struct JoinExt {
+  uint64_t pre, psrc, msg, reserved;
+};
 struct JoinScratch {
   uint64_t* ctl;        // [0] base, [1] the gated message count
   uint64_t* blk;        // [nblk + 1][kBlkFields]; partial 0 holds `base` in field 1
@@ -51,21 +64,43 @@ struct JoinScratch {
   uint2* span;          // [m] a copied message's first and last data frame
   uint64_t* foff;       // [f] bytes of the message before frame f, for every frame inside a copied message's span
   uint32_t* tile_msg;   // [t] the message that holds the first byte of output tile t (tiles count from `base`)
+  // the carry's tables (n_conns != 0), the connection in the message's place
+  uint64_t* cctl;       // [0] 0, [1] the gated connection count
+  uint64_t* cblk;       // [nblkc][kCarryFields]
+  JoinExt* ext;         // [m] a copied message's carried prefix
+  JoinExt* cext;        // [c] an OPEN carry's prefix and the message its frames belong to
+  gevws_body* cbody;    // [c] an OPEN carry's place in d_carry_dst as a JOINED body record
+  uint64_t* cdst;       // [c] as mdst
+  uint2* cspan;         // [c] as span
+  uint32_t* ctile;      // [t] as tile_msg
   size_t zero_bytes, total;
 };
+constexpr int kCarryFields = 5;  // OPEN records, arena bytes, lengths, ERR_TOO_BIG, malformed records
 inline JoinScratch join_scratch(void* base, uint64_t max_frames, uint64_t max_messages, uint32_t nblk,
-                                uint64_t out_cap) {
+                                uint64_t out_cap, uint32_t n_conns = 0, uint32_t nblkc = 0, uint64_t carry_cap = 0) {
   auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
   uint8_t* p = static_cast<uint8_t*>(base);
-  JoinScratch s;
+  JoinScratch s{};
   size_t o = 0;
   s.ctl = reinterpret_cast<uint64_t*>(p + o), o += 256;
   s.blk = reinterpret_cast<uint64_t*>(p + o), o += up((size_t)(nblk + 1) * kBlkFields * sizeof(uint64_t));
+  if (n_conns) {
+    s.cctl = reinterpret_cast<uint64_t*>(p + o), o += 256;
+    s.cblk = reinterpret_cast<uint64_t*>(p + o), o += up((size_t)nblkc * kCarryFields * sizeof(uint64_t));
+  }
   s.zero_bytes = o;
   s.mdst = reinterpret_cast<uint64_t*>(p + o), o += up(max_messages * 8);
   s.span = reinterpret_cast<uint2*>(p + o), o += up(max_messages * 8);
   s.foff = reinterpret_cast<uint64_t*>(p + o), o += up(max_frames * 8);
   s.tile_msg = reinterpret_cast<uint32_t*>(p + o), o += up((out_cap / kTile + 2) * 4);
+  if (n_conns) {
+    s.ext = reinterpret_cast<JoinExt*>(p + o), o += up(max_messages * 32);
+    s.cext = reinterpret_cast<JoinExt*>(p + o), o += up((size_t)n_conns * 32);
+    s.cbody = reinterpret_cast<gevws_body*>(p + o), o += up((size_t)n_conns * 32);
+    s.cdst = reinterpret_cast<uint64_t*>(p + o), o += up((size_t)n_conns * 8);
+    s.cspan = reinterpret_cast<uint2*>(p + o), o += up((size_t)n_conns * 8);
+    s.ctile = reinterpret_cast<uint32_t*>(p + o), o += up((carry_cap / kTile + 2) * 4);
+  }
   s.total = o;
   return s;
 }
@@ -100,6 +135,39 @@ __device__ __forceinline__ JoinDec join_decide(const gevws_message& m, const gev
   return d;
 }
 
+// The carry arguments of the body side's <true> kernels.
+struct JoinCarryIn {
+  const gevws_carry* __restrict__ carry_in;  // may be null
+  uint32_t n_conns;
+  uint64_t max_bytes;
+};
+// join_decide with the connection's carry: a continued message that ends here
+// is delivered behind its carried bytes (pre / psrc: where they are).
+__device__ __forceinline__ JoinDec join_decide_carry(const gevws_message& m,
+                                                     const gevws_inflated* __restrict__ inflated, uint64_t idx,
+                                                     uint32_t call_flags, const JoinCarryIn& ca, uint64_t& pre,
+                                                     uint64_t& psrc) {
+  JoinDec d = join_decide(m, inflated, idx, call_flags);
+  pre = psrc = 0;
+  if ((m.flags & (GEVWS_MSG_BEGIN | GEVWS_MSG_COMPRESSED)) || !ca.carry_in || m.conn >= ca.n_conns) return d;
+  const gevws_carry ci = ca.carry_in[m.conn];
+  if (ci.flags & GEVWS_CARRY_OPEN) {
+    if ((m.flags & GEVWS_MSG_END) && m.status == GEVWS_MSG_OK) {
+      const uint64_t total = ci.length + m.length;
+      if (total >= ci.length && total <= ca.max_bytes) {
+        d.length = total, d.copy = true;
+        d.flags = GEVWS_BODY_WHOLE | GEVWS_BODY_JOINED;
+        pre = ci.length, psrc = ci.off;
+      } else {
+        d.status = GEVWS_MSG_ERR_TOO_BIG;
+      }
+    }
+  } else if ((ci.flags & GEVWS_CARRY_LOST) && ci.status) {
+    d.status = ci.status;
+  }
+  return d;
+}
+
 // The messages of the call: the message pass's count, none when it or a given inflate failed.
 __device__ __forceinline__ uint64_t join_count(uint64_t max_messages, const gevws_summary* __restrict__ msg_sum,
                                                const gevws_summary* __restrict__ inf_sum) {
@@ -107,41 +175,51 @@ __device__ __forceinline__ uint64_t join_count(uint64_t max_messages, const gevw
   return gated_count(max_messages, msg_sum);
 }
 
-// The workgroup's partial {vals[0], vals[1], vals[2], 0} -> blk[row].
-__device__ __forceinline__ void block_partial(const uint64_t (&vals)[3], uint64_t* __restrict__ blk, uint64_t row) {
-  __shared__ uint64_t s_part[3][kWalkBlock / 64];
+// The workgroup's partial {vals[0], .. vals[NV - 1], 0 ..} -> blk[row] (rows of NF fields).
+template <int NV, int NF = kBlkFields>
+__device__ __forceinline__ void block_partial(const uint64_t (&vals)[NV], uint64_t* __restrict__ blk, uint64_t row) {
+  __shared__ uint64_t s_part[NV][kWalkBlock / 64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < NV; ++k) {
     const uint64_t sm = wave_sum(vals[k]);
     if (lane == 0) s_part[k][wv] = sm;
   }
   __syncthreads();
-  if (threadIdx.x < 3) {
+  if (threadIdx.x < NV) {
     uint64_t sm = 0;
     for (int j = 0; j < kWalkBlock / 64; ++j) sm += s_part[threadIdx.x][j];
-    blk[row * kBlkFields + threadIdx.x] = sm;
+    blk[row * NF + threadIdx.x] = sm;
   }
 }
 
 // ------------------------------------------------------------------ 1. sizes
+template <bool CARRY>
 __global__ __launch_bounds__(kWalkBlock) void k_join_size(const gevws_message* __restrict__ msgs,
                                                           uint64_t max_messages,
                                                           const gevws_summary* __restrict__ msg_sum,
                                                           const gevws_inflated* __restrict__ inflated,
                                                           const gevws_summary* __restrict__ inf_sum,
                                                           uint32_t call_flags, uint64_t* __restrict__ ctl,
-                                                          uint64_t* __restrict__ blk) {
+                                                          uint64_t* __restrict__ blk, JoinCarryIn ca) {
   const uint64_t n = join_count(max_messages, msg_sum, inf_sum);
   const uint64_t m = (uint64_t)blockIdx.x * kWalkBlock + threadIdx.x;
-  uint64_t vals[3] = {0, 0, 0};  // delivered, bytes taken in d_out, delivered length
+  uint64_t vals[CARRY ? 4 : 3] = {};  // delivered, bytes taken in d_out, delivered length; CARRY: malformed records
   if (m < n) {
-    const JoinDec d = join_decide(msgs[m], inflated, m, call_flags);
+    JoinDec d;
+    if constexpr (CARRY) {
+      const gevws_message msg = msgs[m];
+      uint64_t pre, psrc;
+      d = join_decide_carry(msg, inflated, m, call_flags, ca, pre, psrc);
+      vals[3] = msg.conn >= ca.n_conns;  // (the verdict pass moves the count out of `errors`)
+    } else {
+      d = join_decide(msgs[m], inflated, m, call_flags);
+    }
     vals[0] = d.flags ? 1 : 0;
     vals[1] = d.copy ? round16(d.length) : 0;
     vals[2] = d.length;
   }
-  block_partial(vals, blk, (uint64_t)blockIdx.x + 1);
+  block_partial<CARRY ? 4 : 3>(vals, blk, (uint64_t)blockIdx.x + 1);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     // joined bodies start behind the inflate's bytes (a call without messages reads none of its inputs)
     const uint64_t base = n && inf_sum ? round16(inf_sum->payload_bytes) : 0;
@@ -152,6 +230,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_join_size(const gevws_message* _
 }
 
 // ------------------------------------------------------------------ 2. records and maps
+template <bool CARRY>
 __global__ __launch_bounds__(kWalkBlock) void k_join_place(const gevws_frame* __restrict__ fr, uint64_t max_frames,
                                                            const gevws_message* __restrict__ msgs,
                                                            const int64_t* __restrict__ msg_of,
@@ -162,17 +241,23 @@ __global__ __launch_bounds__(kWalkBlock) void k_join_place(const gevws_frame* __
                                                            gevws_body* __restrict__ bodies,
                                                            uint64_t* __restrict__ mdst, uint2* __restrict__ span,
                                                            uint64_t* __restrict__ foff,
-                                                           uint32_t* __restrict__ tile_msg) {
+                                                           uint32_t* __restrict__ tile_msg, JoinCarryIn ca,
+                                                           const gevws_summary* __restrict__ carry_sum,
+                                                           JoinExt* __restrict__ ext) {
   if (sum->status != GEVWS_OK) return;  // capacity: nothing written
+  if constexpr (CARRY)
+    if (carry_sum->status != GEVWS_OK) return;  // either side failing suppresses both
   const uint64_t n = ctl[1], base = ctl[0];
   const uint64_t m = (uint64_t)blockIdx.x * kWalkBlock + threadIdx.x;
   gevws_message msg;
   memset(&msg, 0, sizeof(msg));
   JoinDec d;
   memset(&d, 0, sizeof(d));
+  uint64_t pre = 0, psrc = 0;
   if (m < n) {
     msg = msgs[m];
-    d = join_decide(msg, inflated, m, call_flags);
+    if constexpr (CARRY) d = join_decide_carry(msg, inflated, m, call_flags, ca, pre, psrc);
+    else d = join_decide(msg, inflated, m, call_flags);
   }
   const uint64_t padded = d.copy ? round16(d.length) : 0;
   const uint64_t v[1] = {padded};
@@ -194,10 +279,12 @@ __global__ __launch_bounds__(kWalkBlock) void k_join_place(const gevws_frame* __
     else b.off = msg.first_frame < max_frames ? fr[msg.first_frame].payload_off : 0;  // its one frame's slot
   }
   bodies[m] = b;
+  if constexpr (CARRY) ext[m] = JoinExt{pre, psrc, m, 0};
   if (!padded) return;
   // the frames' running offsets; control frames in between get theirs too, so
   // the array never decreases over the span and a bisection finds a byte's frame
-  uint64_t run = 0, last = msg.first_frame;
+  // (CARRY: the carried bytes are one more fragment in front of first_frame)
+  uint64_t run = CARRY ? pre : 0, last = msg.first_frame;
   uint32_t seen = 0;
   for (uint64_t f0 = msg.first_frame; f0 < max_frames && seen < msg.nframes; f0 += 4) {
     int64_t ofb[4];
@@ -228,6 +315,10 @@ struct JoinMaps {
   const uint64_t* __restrict__ foff;
   const uint8_t* __restrict__ payload;
   uint64_t nframes;
+  // CARRY: the bodies' carried prefixes
+  const JoinExt* __restrict__ ext;
+  const uint8_t* __restrict__ carry_src;
+  uint64_t carry_src_bytes;
 };
 // One fragment's counted bytes: d_out[ds, de) come from src[0, de - ds).
 struct JoinFrag {
@@ -238,6 +329,7 @@ struct JoinFrag {
 
 // The fragment that holds byte x of d_out, x inside a copied body of a
 // message in [mlo, mhi]; false: x is a pad byte.
+template <bool CARRY>
 __device__ __forceinline__ bool join_lookup(const JoinMaps& M, uint64_t x, uint64_t mlo, uint64_t mhi, JoinFrag& g) {
   uint64_t lo = mlo, hi = mhi;
   while (lo < hi) {  // the last message that starts at or before x: the later ones at its place take no space
@@ -250,6 +342,19 @@ __device__ __forceinline__ bool join_lookup(const JoinMaps& M, uint64_t x, uint6
   const uint64_t pos = x - b.off;
   const uint2 sp = M.span[lo];
   uint64_t flo = sp.x, fhi = sp.y;
+  uint64_t owner = lo;  // the message its frames map to in msg_of
+  if constexpr (CARRY) {
+    const JoinExt e = M.ext[lo];
+    owner = e.msg;
+    if (pos < e.pre) {  // below foff[first_frame]: the prefix, a fragment whose successor is first_frame
+      if (e.psrc > M.carry_src_bytes || e.pre > M.carry_src_bytes - e.psrc) return false;
+      const bool frames = flo <= fhi && fhi < M.nframes;
+      g.ds = b.off, g.de = b.off + e.pre;
+      g.src = M.carry_src + e.psrc;
+      g.m = owner, g.f = frames ? flo - 1 : 1, g.last = frames ? fhi : 0, g.body_end = b.off + b.length;
+      return true;
+    }
+  }
   if (fhi >= M.nframes || flo > fhi) return false;
   const uint64_t last = fhi;
   while (flo < fhi) {  // the last frame that starts at or before pos: it holds the byte
@@ -263,7 +368,7 @@ __device__ __forceinline__ bool join_lookup(const JoinMaps& M, uint64_t x, uint6
   g.ds = b.off + fo;
   g.de = g.ds + len;
   g.src = M.payload + rec.payload_off;
-  g.m = lo, g.f = flo, g.last = last, g.body_end = b.off + b.length;
+  g.m = owner, g.f = flo, g.last = last, g.body_end = b.off + b.length;
   return true;
 }
 
@@ -290,11 +395,12 @@ __device__ __forceinline__ bool join_next(const JoinMaps& M, JoinFrag& g) {
 }
 
 // seed: a fragment that may hold x (the wave's current one), or null.
+template <bool CARRY>
 __device__ __forceinline__ u32x4 join_vector(const JoinMaps& M, uint64_t x, uint64_t mlo, uint64_t mhi,
                                              const JoinFrag* seed) {
   JoinFrag g;
   if (seed && x >= seed->ds && x < seed->de) g = *seed;
-  else if (!join_lookup(M, x, mlo, mhi, g)) return u32x4{0, 0, 0, 0};  // a whole vector of pad
+  else if (!join_lookup<CARRY>(M, x, mlo, mhi, g)) return u32x4{0, 0, 0, 0};  // a whole vector of pad
   u128 acc = 0;
   uint64_t p = x;
   for (;;) {
@@ -321,6 +427,7 @@ __device__ __forceinline__ void uniform_frag(JoinFrag& g) {
   g.m = uniform64(g.m), g.f = uniform64(g.f), g.last = uniform64(g.last), g.body_end = uniform64(g.body_end);
 }
 
+template <bool CARRY>
 __global__ __launch_bounds__(kJoinBlock) void k_join_copy(const gevws_frame* __restrict__ fr, uint64_t max_frames,
                                                           const int64_t* __restrict__ msg_of,
                                                           const uint8_t* __restrict__ payload,
@@ -331,11 +438,17 @@ __global__ __launch_bounds__(kJoinBlock) void k_join_copy(const gevws_frame* __r
                                                           const uint32_t* __restrict__ tile_msg,
                                                           const uint64_t* __restrict__ ctl,
                                                           const gevws_summary* __restrict__ sum,
-                                                          uint8_t* __restrict__ out) {
+                                                          uint8_t* __restrict__ out,
+                                                          const gevws_summary* __restrict__ other_sum,
+                                                          const JoinExt* __restrict__ ext,
+                                                          const uint8_t* __restrict__ carry_src,
+                                                          uint64_t carry_src_bytes) {
   if (sum->status != GEVWS_OK) return;
+  if constexpr (CARRY)
+    if (other_sum->status != GEVWS_OK) return;  // either side failing suppresses both
   const uint64_t base = ctl[0], n = ctl[1], end = sum->payload_bytes;  // the joined region is d_out[base, end)
   if (end <= base || n == 0) return;
-  const JoinMaps M{fr, msg_of, bodies, mdst, span, foff, payload, max_frames};
+  const JoinMaps M{fr, msg_of, bodies, mdst, span, foff, payload, max_frames, ext, carry_src, carry_src_bytes};
   const uint64_t ntiles = (end - base + kTile - 1) / kTile;
   // a workgroup's run of tiles is its four waves' runs, one behind the other
   const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -355,7 +468,7 @@ __global__ __launch_bounds__(kJoinBlock) void k_join_copy(const gevws_frame* __r
       // a few long fragments on in the same body: no bisection
       if (have && T >= g.de && T < g.body_end && g.de - g.ds >= kJoinRowBytes)
         for (int k = 0; k < kJoinWalk && !found && join_next(M, g); ++k) found = T < g.de;
-      if (!found) found = join_lookup(M, T, mlo, mhi, g);
+      if (!found) found = join_lookup<CARRY>(M, T, mlo, mhi, g);
       have = found;
       uniform_frag(g);
     }
@@ -386,7 +499,7 @@ __global__ __launch_bounds__(kJoinBlock) void k_join_copy(const gevws_frame* __r
       for (int u = 0; u < kJoinVecs; ++u) {
         const uint64_t xu = T + (uint64_t)u * 1024 + (uint64_t)lane * 16;
         if (!((done >> u) & 1) && xu < end && xu >= g.ds && xu < g.de)
-          st16_nt(out + xu, join_vector(M, xu, mlo, mhi, &g)), done |= 1u << u;
+          st16_nt(out + xu, join_vector<CARRY>(M, xu, mlo, mhi, &g)), done |= 1u << u;
       }
       // on to the body's next fragment while fragments are long enough for whole rows of the wave
       if (!join_next(M, g)) {
@@ -399,9 +512,175 @@ __global__ __launch_bounds__(kJoinBlock) void k_join_copy(const gevws_frame* __r
 #pragma unroll 1
     for (int u = 0; u < kJoinVecs; ++u) {
       const uint64_t xu = T + (uint64_t)u * 1024 + (uint64_t)lane * 16;
-      if (!((done >> u) & 1) && xu < end) st16_nt(out + xu, join_vector(M, xu, mlo, mhi, nullptr));
+      if (!((done >> u) & 1) && xu < end) st16_nt(out + xu, join_vector<CARRY>(M, xu, mlo, mhi, nullptr));
     }
   }
+}
+
+// ------------------------------------------------------------------ the carry side
+static_assert(sizeof(gevws_carry) == 32 && offsetof(gevws_carry, length) == 8 && offsetof(gevws_carry, opcode) == 16 &&
+                  offsetof(gevws_carry, flags) == 17 && offsetof(gevws_carry, status) == 18 &&
+                  offsetof(gevws_carry, reserved) == 19 && sizeof(JoinExt) == 32, "gevws_carry layout");
+
+// What becomes of connection c's carry.
+struct CarryDec {
+  uint64_t length, pre, psrc;  // OPEN: the bytes kept, of which the first `pre` are carried in from psrc
+  int64_t msg;                 // the open message whose frames follow the prefix, or -1
+  uint32_t too_big;            // bodies and carries of the connection that became ERR_TOO_BIG
+  uint8_t opcode, flags, status;
+  bool invalid;
+};
+struct CarryIn {
+  const gevws_message* __restrict__ msgs;
+  const gevws_conn_msg* __restrict__ conn_msg;
+  const gevws_carry* __restrict__ carry_in;  // may be null
+  uint64_t carry_src_bytes, max_bytes;
+  uint32_t n_conns;
+};
+// n: the gated message count.  Nothing is indexed by a field before it is checked.
+__device__ __forceinline__ CarryDec carry_decide(const CarryIn& in, uint32_t c, uint64_t n) {
+  CarryDec d;
+  memset(&d, 0, sizeof(d));
+  d.msg = -1;
+  const gevws_conn_msg cm = in.conn_msg[c];
+  gevws_carry ci;
+  memset(&ci, 0, sizeof(ci));
+  if (in.carry_in) ci = in.carry_in[c];
+  if ((ci.flags & GEVWS_CARRY_OPEN) &&
+      ((ci.off & 15) || ci.off > in.carry_src_bytes || ci.length > in.carry_src_bytes - ci.off))
+    d.invalid = true;
+  else if (cm.first_message > n || cm.nmessages > n - cm.first_message)
+    d.invalid = true;
+  if (d.invalid) return d;
+  if (cm.nmessages) {  // the body side's verdict on a continued message that ends here
+    const gevws_message f = in.msgs[cm.first_message];
+    if (!(f.flags & (GEVWS_MSG_BEGIN | GEVWS_MSG_COMPRESSED)) && (f.flags & GEVWS_MSG_END) &&
+        f.status == GEVWS_MSG_OK && (ci.flags & GEVWS_CARRY_OPEN) &&
+        (ci.length + f.length < ci.length || ci.length + f.length > in.max_bytes))
+      d.too_big = 1;
+  }
+  if (cm.error != 0) return d;  // the carry is dropped
+  if (cm.nmessages == 0) {      // the record moves forward
+    if (ci.flags & GEVWS_CARRY_OPEN) {
+      d.flags = GEVWS_CARRY_OPEN, d.opcode = ci.opcode;
+      d.length = d.pre = ci.length, d.psrc = ci.off;
+    } else if (ci.flags & GEVWS_CARRY_LOST) {
+      d.flags = GEVWS_CARRY_LOST, d.opcode = ci.opcode, d.status = ci.status;
+    }
+  } else {
+    const uint64_t li = cm.first_message + cm.nmessages - 1;
+    const gevws_message l = in.msgs[li];
+    if (l.flags & GEVWS_MSG_END) return d;
+    d.opcode = l.opcode;
+    const bool begin = l.flags & GEVWS_MSG_BEGIN;
+    if (l.flags & GEVWS_MSG_COMPRESSED) {
+      d.flags = GEVWS_CARRY_LOST;
+      d.status = !begin && (ci.flags & GEVWS_CARRY_LOST) ? ci.status : 0;
+    } else if (begin) {
+      d.flags = GEVWS_CARRY_OPEN, d.length = l.length, d.msg = (int64_t)li;
+    } else if (ci.flags & GEVWS_CARRY_OPEN) {
+      d.flags = GEVWS_CARRY_OPEN, d.pre = ci.length, d.psrc = ci.off, d.msg = (int64_t)li;
+      d.length = ci.length + l.length;
+      if (d.length < ci.length) d.length = UINT64_MAX;  // (over any limit)
+    } else {
+      d.flags = GEVWS_CARRY_LOST;
+      d.status = (ci.flags & GEVWS_CARRY_LOST) ? ci.status : 0;
+    }
+  }
+  if ((d.flags & GEVWS_CARRY_OPEN) && d.length > in.max_bytes) {
+    d.flags = GEVWS_CARRY_LOST, d.status = GEVWS_MSG_ERR_TOO_BIG;
+    d.length = d.pre = d.psrc = 0, d.msg = -1;
+    d.too_big += 1;
+  }
+  return d;
+}
+// The connections of the call: all of them, none when the message pass or a given inflate failed.
+__device__ __forceinline__ bool carry_gate(const gevws_summary* __restrict__ msg_sum,
+                                           const gevws_summary* __restrict__ inf_sum) {
+  return !(msg_sum && msg_sum->status != GEVWS_OK) && !(inf_sum && inf_sum->status != GEVWS_OK);
+}
+
+__global__ __launch_bounds__(kWalkBlock) void k_carry_size(CarryIn in, uint64_t max_messages,
+                                                           const gevws_summary* __restrict__ msg_sum,
+                                                           const gevws_summary* __restrict__ inf_sum,
+                                                           uint64_t* __restrict__ cctl, uint64_t* __restrict__ cblk) {
+  const bool open = carry_gate(msg_sum, inf_sum);
+  const uint64_t n = open ? gated_count(max_messages, msg_sum) : 0;
+  const uint64_t c = (uint64_t)blockIdx.x * kWalkBlock + threadIdx.x;
+  uint64_t vals[kCarryFields] = {};
+  if (open && c < in.n_conns) {
+    const CarryDec d = carry_decide(in, (uint32_t)c, n);
+    const bool keep = d.flags & GEVWS_CARRY_OPEN;
+    vals[0] = keep, vals[1] = keep ? round16(d.length) : 0, vals[2] = keep ? d.length : 0;
+    vals[3] = d.too_big, vals[4] = d.invalid;
+  }
+  block_partial<kCarryFields, kCarryFields>(vals, cblk, blockIdx.x);
+  if (blockIdx.x == 0 && threadIdx.x == 0) cctl[0] = 0, cctl[1] = open ? in.n_conns : 0;
+}
+
+// Behind both scans, one lane: the gates' status or ERR_INVALID into both
+// summaries, before a place pass could write.  The scans left the malformed
+// messages in body->errors and the malformed connections in carry->run_frames.
+__global__ void k_carry_verdict(const gevws_summary* __restrict__ msg_sum, const gevws_summary* __restrict__ inf_sum,
+                                gevws_summary* __restrict__ body, gevws_summary* __restrict__ carry) {
+  gevws_summary a = *body, b = *carry, z;
+  memset(&z, 0, sizeof(z));
+  const uint64_t bad = a.errors + b.run_frames;
+  a.errors = 0, b.run_frames = 0;
+  if (msg_sum && msg_sum->status != GEVWS_OK) z.status = msg_sum->status, a = b = z;
+  else if (inf_sum && inf_sum->status != GEVWS_OK) z.status = inf_sum->status, a = b = z;
+  else if (bad) z.errors = bad, z.status = GEVWS_ERR_INVALID, a = b = z;
+  *body = a;
+  *carry = b;
+}
+
+__global__ __launch_bounds__(kWalkBlock) void k_carry_place(
+    const gevws_frame* __restrict__ fr, uint64_t max_frames, const int64_t* __restrict__ msg_of, CarryIn in,
+    uint64_t max_messages, const gevws_summary* __restrict__ msg_sum, const uint64_t* __restrict__ cblk,
+    const gevws_summary* __restrict__ sum, const gevws_summary* __restrict__ body_sum,
+    gevws_carry* __restrict__ carry_out, gevws_body* __restrict__ cbody, uint64_t* __restrict__ cdst,
+    uint2* __restrict__ cspan, JoinExt* __restrict__ cext, uint64_t* __restrict__ foff,
+    uint32_t* __restrict__ ctile) {
+  if (sum->status != GEVWS_OK || body_sum->status != GEVWS_OK) return;  // either side failing suppresses both
+  const uint64_t n = gated_count(max_messages, msg_sum);
+  const uint64_t c = (uint64_t)blockIdx.x * kWalkBlock + threadIdx.x;
+  CarryDec d;
+  memset(&d, 0, sizeof(d));
+  if (c < in.n_conns) d = carry_decide(in, (uint32_t)c, n);
+  const bool keep = d.flags & GEVWS_CARRY_OPEN;
+  const uint64_t padded = keep ? round16(d.length) : 0;
+  const uint64_t v[1] = {padded};
+  uint64_t ex[1], tot[1];
+  block_excl_scan<kWalkBlock, 1>(v, ex, tot);
+  if (c >= in.n_conns) return;
+  const uint64_t dst = cblk[(uint64_t)blockIdx.x * kCarryFields + 1] + ex[0];
+  cdst[c] = dst;
+  gevws_carry o;
+  memset(&o, 0, sizeof(o));
+  gevws_body b;
+  memset(&b, 0, sizeof(b));
+  if (d.flags) o.opcode = d.opcode, o.flags = d.flags, o.status = d.status;
+  if (keep) {
+    o.off = b.off = dst, o.length = b.length = d.length;
+    b.conn = (uint32_t)c, b.opcode = d.opcode, b.flags = GEVWS_BODY_WHOLE | GEVWS_BODY_JOINED;
+  }
+  carry_out[c] = o;
+  cbody[c] = b;
+  cext[c] = JoinExt{d.pre, d.psrc, (uint64_t)d.msg, 0};
+  if (!padded) return;
+  uint2 sp = make_uint2(1, 0);  // no frames: the carried bytes alone
+  if (d.msg >= 0) {
+    const gevws_message msg = in.msgs[d.msg];
+    uint64_t run = d.pre, last = msg.first_frame;
+    uint32_t seen = 0;
+    for (uint64_t f = msg.first_frame; f < max_frames && seen < msg.nframes; ++f) {
+      foff[f] = run;
+      if (msg_of[f] == d.msg) run += (uint64_t)fr[f].hdr.length, ++seen, last = f;
+    }
+    sp = make_uint2((uint32_t)msg.first_frame, (uint32_t)last);
+  }
+  cspan[c] = sp;
+  for (uint64_t t = (dst + kTile - 1) / kTile; t * kTile < dst + padded; ++t) ctile[t] = (uint32_t)c;
 }
 
 // ------------------------------------------------------------------ the reply step
@@ -440,7 +719,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_reply_count(const gevws_body* __
     const ReplyDec r = reply_decide(bodies[m], policy, conn_ext, n_conns);
     vals[0] = r.reply && r.deflate, vals[1] = r.reply && !r.deflate, vals[2] = r.bad;
   }
-  block_partial(vals, blk, blockIdx.x);
+  block_partial<3>(vals, blk, blockIdx.x);
 }
 
 // The scan left {deflate entries, plain entries, malformed} in *def_sum's
@@ -527,11 +806,92 @@ extern "C" int gevws_join_async(gevws_ctx* ctx, void* stream, const gevws_frame*
                                 const gevws_inflated* d_inflated, const gevws_summary* d_inflate_summary,
                                 uint32_t flags, gevws_body* d_bodies, uint8_t* d_out, uint64_t out_cap,
                                 gevws_summary* d_summary) {
+  return gevws_join_carry_async(ctx, stream, d_frames, max_frames, d_messages, max_messages, d_msg_of, d_msg_summary,
+                                d_payload, d_inflated, d_inflate_summary, flags, d_bodies, d_out, out_cap, d_summary,
+                                nullptr, 0, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr);
+}
+
+// The call with a carry: both sides' size / scan, the verdict, both sides' place, both gathers.
+static int join_with_carry(gevws_ctx* ctx, hipStream_t st, const gevws_frame* d_frames, uint64_t max_frames,
+                           const gevws_message* d_messages, uint64_t max_messages, const int64_t* d_msg_of,
+                           const gevws_summary* d_msg_summary, const uint8_t* d_payload,
+                           const gevws_inflated* d_inflated, const gevws_summary* d_inflate_summary, uint32_t flags,
+                           gevws_body* d_bodies, uint8_t* d_out, uint64_t out_cap, gevws_summary* d_summary,
+                           const gevws_conn_msg* d_conn_msg, uint32_t n_conns, uint64_t max_message_bytes,
+                           const gevws_carry* d_carry_in, const uint8_t* d_carry_src, uint64_t carry_src_bytes,
+                           gevws_carry* d_carry_out, uint8_t* d_carry_dst, uint64_t carry_cap,
+                           gevws_summary* d_carry_summary) {
+  if (max_message_bytes == 0 || max_message_bytes > 0xFFFFFFFFull || (reinterpret_cast<uintptr_t>(d_carry_dst) & 15) ||
+      (reinterpret_cast<uintptr_t>(d_carry_src) & 15) || (d_carry_in && carry_src_bytes && !d_carry_src))
+    return GEVWS_ERR_INVALID;
+  if (n_conns == 0) {
+    GEVWS_HIP(hipMemsetAsync(d_summary, 0, sizeof(gevws_summary), st));
+    GEVWS_HIP(hipMemsetAsync(d_carry_summary, 0, sizeof(gevws_summary), st));
+    return GEVWS_OK;
+  }
+  if (max_messages &&
+      (!d_frames || !d_messages || !d_msg_of || !d_msg_summary || !d_payload || !d_bodies || !d_out ||
+       (reinterpret_cast<uintptr_t>(d_payload) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15)))
+    return GEVWS_ERR_INVALID;
+  const uint32_t nblk = (uint32_t)((max_messages + kWalkBlock - 1) / kWalkBlock);
+  const uint32_t nblkc = (n_conns + kWalkBlock - 1) / kWalkBlock;
+  int r = order_after_last(ctx, st);
+  if (r != GEVWS_OK) return r;
+  r = ensure_scratch(ctx, join_scratch(nullptr, max_frames, max_messages, nblk, out_cap, n_conns, nblkc, carry_cap).total);
+  if (r != GEVWS_OK) return r;
+  const JoinScratch s = join_scratch(ctx->scratch, max_frames, max_messages, nblk, out_cap, n_conns, nblkc, carry_cap);
+  const JoinCarryIn ca{d_carry_in, n_conns, max_message_bytes};
+  const CarryIn in{d_messages, d_conn_msg, d_carry_in, carry_src_bytes, max_message_bytes, n_conns};
+  const uint32_t grid = (uint32_t)ctx->num_cus * kJoinWgPerCU;
+  GEVWS_HIP(hipMemsetAsync(s.ctl, 0, s.zero_bytes, st));
+  if (max_messages) {
+    k_join_size<true><<<nblk, kWalkBlock, 0, st>>>(d_messages, max_messages, d_msg_summary, d_inflated,
+                                                   d_inflate_summary, flags, s.ctl, s.blk, ca);
+    k_scan_blocks<false><<<1, kScanBlock, 0, st>>>(s.blk, nblk + 1, UINT64_MAX, out_cap, d_summary);
+  } else {
+    GEVWS_HIP(hipMemsetAsync(d_summary, 0, sizeof(gevws_summary), st));
+  }
+  k_carry_size<<<nblkc, kWalkBlock, 0, st>>>(in, max_messages, d_msg_summary, d_inflate_summary, s.cctl, s.cblk);
+  k_scan_blocks<false, kCarryFields, kWalkBlock><<<1, kWalkBlock, 0, st>>>(s.cblk, nblkc, UINT64_MAX, carry_cap, d_carry_summary);
+  k_carry_verdict<<<1, 1, 0, st>>>(d_msg_summary, d_inflate_summary, d_summary, d_carry_summary);
+  if (max_messages)
+    k_join_place<true><<<nblk, kWalkBlock, 0, st>>>(d_frames, max_frames, d_messages, d_msg_of, d_inflated, flags,
+                                                    s.ctl, s.blk, d_summary, d_bodies, s.mdst, s.span, s.foff,
+                                                    s.tile_msg, ca, d_carry_summary, s.ext);
+  k_carry_place<<<nblkc, kWalkBlock, 0, st>>>(d_frames, max_frames, d_msg_of, in, max_messages, d_msg_summary, s.cblk,
+                                              d_carry_summary, d_summary, d_carry_out, s.cbody, s.cdst, s.cspan,
+                                              s.cext, s.foff, s.ctile);
+  if (max_messages)
+    k_join_copy<true><<<grid, kJoinBlock, 0, st>>>(d_frames, max_frames, d_msg_of, d_payload, d_bodies, s.mdst, s.span,
+                                                   s.foff, s.tile_msg, s.ctl, d_summary, d_out, d_carry_summary,
+                                                   s.ext, d_carry_src, carry_src_bytes);
+  k_join_copy<true><<<grid, kJoinBlock, 0, st>>>(d_frames, max_frames, d_msg_of, d_payload, s.cbody, s.cdst, s.cspan,
+                                                 s.foff, s.ctile, s.cctl, d_carry_summary, d_carry_dst, d_summary,
+                                                 s.cext, d_carry_src, carry_src_bytes);
+  GEVWS_HIP(hipGetLastError());
+  return mark_last(ctx, st);
+}
+
+extern "C" int gevws_join_carry_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames, uint64_t max_frames,
+                                      const gevws_message* d_messages, uint64_t max_messages, const int64_t* d_msg_of,
+                                      const gevws_summary* d_msg_summary, const uint8_t* d_payload,
+                                      const gevws_inflated* d_inflated, const gevws_summary* d_inflate_summary,
+                                      uint32_t flags, gevws_body* d_bodies, uint8_t* d_out, uint64_t out_cap,
+                                      gevws_summary* d_summary, const gevws_conn_msg* d_conn_msg, uint32_t n_conns,
+                                      uint64_t max_message_bytes, const gevws_carry* d_carry_in,
+                                      const uint8_t* d_carry_src, uint64_t carry_src_bytes, gevws_carry* d_carry_out,
+                                      uint8_t* d_carry_dst, uint64_t carry_cap, gevws_summary* d_carry_summary) {
   if (!ctx || !d_summary || (flags & ~GEVWS_JOIN_ALL) || max_frames > 0xFFFFFFFFull ||
       max_messages > 0x7FFFFFFFull * kWalkBlock)
     return GEVWS_ERR_INVALID;
   DeviceGuard g(ctx->device);
   hipStream_t st = pick_stream(ctx, stream);
+  if (d_conn_msg && d_carry_out && d_carry_dst && d_carry_summary)
+    return join_with_carry(ctx, st, d_frames, max_frames, d_messages, max_messages, d_msg_of, d_msg_summary, d_payload,
+                           d_inflated, d_inflate_summary, flags, d_bodies, d_out, out_cap, d_summary, d_conn_msg,
+                           n_conns, max_message_bytes, d_carry_in, d_carry_src, carry_src_bytes, d_carry_out,
+                           d_carry_dst, carry_cap, d_carry_summary);
+  // the NULL call: gevws_join_async
   if (max_messages == 0) {
     GEVWS_HIP(hipMemsetAsync(d_summary, 0, sizeof(gevws_summary), st));
     return GEVWS_OK;
@@ -547,14 +907,16 @@ extern "C" int gevws_join_async(gevws_ctx* ctx, void* stream, const gevws_frame*
   if (r != GEVWS_OK) return r;
   const JoinScratch s = join_scratch(ctx->scratch, max_frames, max_messages, nblk, out_cap);
   GEVWS_HIP(hipMemsetAsync(s.ctl, 0, s.zero_bytes, st));
-  k_join_size<<<nblk, kWalkBlock, 0, st>>>(d_messages, max_messages, d_msg_summary, d_inflated, d_inflate_summary,
-                                           flags, s.ctl, s.blk);
+  const JoinCarryIn none{nullptr, 0, 0};
+  k_join_size<false><<<nblk, kWalkBlock, 0, st>>>(d_messages, max_messages, d_msg_summary, d_inflated,
+                                                  d_inflate_summary, flags, s.ctl, s.blk, none);
   k_scan_blocks<false><<<1, kScanBlock, 0, st>>>(s.blk, nblk + 1, UINT64_MAX, out_cap, d_summary);
-  k_join_place<<<nblk, kWalkBlock, 0, st>>>(d_frames, max_frames, d_messages, d_msg_of, d_inflated, flags, s.ctl,
-                                            s.blk, d_summary, d_bodies, s.mdst, s.span, s.foff, s.tile_msg);
-  k_join_copy<<<(uint32_t)ctx->num_cus * kJoinWgPerCU, kJoinBlock, 0, st>>>(
+  k_join_place<false><<<nblk, kWalkBlock, 0, st>>>(d_frames, max_frames, d_messages, d_msg_of, d_inflated, flags,
+                                                   s.ctl, s.blk, d_summary, d_bodies, s.mdst, s.span, s.foff,
+                                                   s.tile_msg, none, nullptr, nullptr);
+  k_join_copy<false><<<(uint32_t)ctx->num_cus * kJoinWgPerCU, kJoinBlock, 0, st>>>(
       d_frames, max_frames, d_msg_of, d_payload, d_bodies, s.mdst, s.span, s.foff, s.tile_msg, s.ctl, d_summary,
-      d_out);
+      d_out, nullptr, nullptr, nullptr, 0);
   GEVWS_HIP(hipGetLastError());
   return mark_last(ctx, st);
 }

@@ -950,8 +950,9 @@ int gevws_deflate_negotiate_takeover(const uint8_t *offer, uint64_t n, uint32_t 
  * a given d_inflate_summary whose status is not GEVWS_OK give a zero summary
  * and read none of the inputs.  Any flag bit but GEVWS_JOIN_ALL is
  * GEVWS_ERR_INVALID from the call; max_frames is at most 2^32 - 1.
- * Out of scope: a message that spans two passes stays undelivered, as it
- * stays GEVWS_INF_PENDING in the inflate. */
+ * A message that spans two passes stays undelivered by this call;
+ * gevws_join_carry_async below keeps a plain one's bytes from pass to pass and
+ * delivers it.  gevws_join_async is that function's NULL call. */
 #define GEVWS_JOIN_ALL 1u          /* call flag: copy single-frame plain messages too */
 #define GEVWS_BODY_WHOLE    1u     /* delivered: off / length are valid */
 #define GEVWS_BODY_JOINED   2u     /* its bytes were written to d_out by this call */
@@ -971,6 +972,116 @@ int gevws_join_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_frames, 
                      const gevws_inflated *d_inflated /* may be NULL */,
                      const gevws_summary *d_inflate_summary /* may be NULL */, uint32_t flags,
                      gevws_body *d_bodies, uint8_t *d_out, uint64_t out_cap, gevws_summary *d_summary);
+
+/* gevws_join_carry_async is gevws_join_async plus a second carry beside
+ * gevws_msg_state: the bytes of each connection's open plain message, kept on
+ * the device between passes, so that a message whose frames arrive over
+ * several passes is delivered with the pass that holds its FIN frame.
+ * Additions to ABI version 3: nothing above changes.
+ *
+ * The carry is a ping-pong between two caller-owned arenas: the (d_carry_out,
+ * d_carry_dst) of one pass are the (d_carry_in, d_carry_src) of the next, with
+ * the carry summary's payload_bytes as carry_src_bytes.  d_carry_dst overlaps
+ * neither d_carry_src nor d_out.  Records and arenas are indexed by the
+ * batch's connection index, as d_state and the takeover slots are.  Both
+ * arenas start on a 16-byte boundary and are read and written as whole 16-byte
+ * vectors (so they are allocated in whole vectors).
+ *
+ * NULL call.  With d_conn_msg, d_carry_out, d_carry_dst or d_carry_summary
+ * NULL the call is gevws_join_async, bit for bit, and looks at none of the
+ * other added arguments.
+ *
+ * Otherwise, with ci = d_carry_in[c] (all-zero when d_carry_in is NULL):
+ *
+ * Continued message (body side).  A message without GEVWS_MSG_BEGIN and
+ * without GEVWS_MSG_COMPRESSED is its connection's first, continued from the
+ * state.  The rule looks at the message alone, like every body's: an error
+ * later in the same batch does not take a finished message back.
+ *   - ci OPEN: its whole body is the carried bytes followed by its data
+ *     frames' bytes (counted as above).  With GEVWS_MSG_END, status OK and a
+ *     total <= max_message_bytes it is delivered WHOLE | JOINED, with or
+ *     without GEVWS_JOIN_ALL, in d_out in message order like every copied
+ *     body; length is the total.  With END and status OK but over the limit it
+ *     is not delivered and its body status is GEVWS_MSG_ERR_TOO_BIG.  Without
+ *     END, or with a failed status, it is undelivered as above.
+ *   - ci LOST: not delivered; its body status is ci.status when that is
+ *     nonzero, else the message's.
+ *   - ci zero: undelivered exactly as in gevws_join_async.
+ * d_summary counts continued deliveries like any other delivered body; its
+ * errors stay 0.
+ *
+ * d_carry_out[c] (carry side), for a connection with d_conn_msg[c].error == 0:
+ *   - Message still open: the connection's last message has no END.  A plain
+ *     message that began in this batch becomes OPEN with its fragments' bytes;
+ *     one that continues an OPEN ci becomes OPEN with the carried bytes
+ *     followed by this batch's fragments.  Over max_message_bytes it becomes
+ *     LOST with status GEVWS_MSG_ERR_TOO_BIG instead.  A compressed message
+ *     that began in this batch becomes LOST with status 0; a continuation of a
+ *     LOST ci becomes LOST with ci.status, of a zero ci LOST with status 0.
+ *     (Compressed messages that span passes stay GEVWS_INF_PENDING in the
+ *     inflate: out of scope.)
+ *   - No message in this batch (nmessages == 0: idle, control frames only,
+ *     decode status < 0): the record moves forward unchanged in meaning -- an
+ *     OPEN one's bytes are copied to d_carry_dst (the limit applies), a LOST
+ *     one stays LOST with its opcode and status, a zero one stays zero.
+ *   - Otherwise all-zero.  So a LOST record lasts until that message's END and
+ *     no longer; the connection's next message is carried and delivered
+ *     normally.
+ * A connection with d_conn_msg[c].error != 0 gets an all-zero record: its
+ * carry is dropped, and the caller closes it.  An OPEN record has off / length
+ * / opcode, a LOST one opcode and status; every other field is zero.
+ *
+ * Layout of d_carry_dst.  OPEN bodies lie in connection order, each on a
+ * 16-byte boundary, the pad behind each zeroed; a zero-length body takes no
+ * space.  Every store is a whole vector inside [0, payload_bytes).
+ *
+ * d_carry_summary: frames = OPEN records written, payload_bytes = bytes of
+ * d_carry_dst used, payload_len = the sum of their lengths, errors = bodies
+ * and carries that became GEVWS_MSG_ERR_TOO_BIG in this call.
+ *
+ * Capacity.  payload_bytes > out_cap, or > carry_cap on the carry side, sets
+ * GEVWS_ERR_CAPACITY in the summary concerned, with the need in it; the other
+ * summary keeps its figures.  Then none of d_bodies, d_out, d_carry_out and
+ * d_carry_dst is written.  The caller retries with the same inputs: the `in`
+ * side is never written.
+ *
+ * Gates.  A failed d_msg_summary, or a given failed d_inflate_summary, copies
+ * its status into both summaries (other fields 0); nothing else is written and
+ * the caller keeps the old carry.  n_conns == 0 gives two zero summaries.
+ * Zero messages with status OK is no gate for the carry side: the carries move
+ * forward, and the body side gives a zero summary (max_messages == 0 too; the
+ * message tables may then be NULL).
+ *
+ * Malformed input, checked before anything is indexed by it: a message with
+ * conn >= n_conns; an OPEN input record with off % 16 != 0 or off + length >
+ * carry_src_bytes; a d_conn_msg[c] whose messages do not lie inside the
+ * message table.  Both summaries then get GEVWS_ERR_INVALID with `errors`
+ * counting such records (a connection once), the other fields zero, and
+ * nothing else is written.  max_message_bytes outside 1 .. 2^32 - 1, an
+ * unknown flag bit, or an arena off its 16-byte boundary is GEVWS_ERR_INVALID
+ * from the call. */
+#define GEVWS_CARRY_OPEN 1u   /* off / length: the open plain message's bytes so far */
+#define GEVWS_CARRY_LOST 2u   /* a message is open but its bytes are not kept; status says why */
+typedef struct gevws_carry {  /* 32 bytes per connection; all-zero = no message open */
+    uint64_t off;      /* into the carry arena, on GEVWS_PAYLOAD_ALIGN */
+    uint64_t length;   /* may be 0 with OPEN: opened by an empty fragment */
+    uint8_t opcode;    /* 1 / 2 */
+    uint8_t flags;     /* GEVWS_CARRY_* */
+    uint8_t status;    /* LOST: GEVWS_MSG_ERR_TOO_BIG, or GEVWS_MSG_OK (compressed, or nothing carried in) */
+    uint8_t reserved[13];
+} gevws_carry;
+int gevws_join_carry_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_frames, uint64_t max_frames,
+                           const gevws_message *d_messages, uint64_t max_messages, const int64_t *d_msg_of,
+                           const gevws_summary *d_msg_summary, const uint8_t *d_payload,
+                           const gevws_inflated *d_inflated /* may be NULL */,
+                           const gevws_summary *d_inflate_summary /* may be NULL */, uint32_t flags,
+                           gevws_body *d_bodies, uint8_t *d_out, uint64_t out_cap, gevws_summary *d_summary,
+                           const gevws_conn_msg *d_conn_msg, uint32_t n_conns,
+                           uint64_t max_message_bytes /* 1 .. 2^32-1 */,
+                           const gevws_carry *d_carry_in /* may be NULL: every connection fresh */,
+                           const uint8_t *d_carry_src, uint64_t carry_src_bytes,
+                           gevws_carry *d_carry_out, uint8_t *d_carry_dst, uint64_t carry_cap,
+                           gevws_summary *d_carry_summary);
 
 /* gevws_reply_bodies_async is the message-level stand-in for the user's
  * handler, as gevws_dispatch_async's policy is at frame level: with

@@ -15,6 +15,12 @@ Join, copy and reply alternate in one process, each timed by HIP events around
 `reps` launches; one JSON line per shape, medians over the rounds.
 
     python tools/bench_join.py [--rounds 7] [--warmup 2] [--shapes c5,small] [--out FILE]
+
+--carry measures gevws_join_carry_async instead: the C5-like shape (64
+connections, one 1 MiB binary message each, fragments up to 64 KiB) with every
+message cut over 2, 4 and 16 passes.  Per pass: the bytes the call moves on
+both sides (lengths read + 16-rounded lengths written), its time, and the ratio
+to gevws_copy_async moving as many bytes; one JSON line per cut.
 """
 from __future__ import annotations
 
@@ -56,6 +62,130 @@ def median(xs):
     return sorted(xs)[len(xs) // 2]
 
 
+def layouts_cut(passes: int, n_conns: int = 64, message_bytes: int = 1 << 20, max_fragment: int = 65536,
+                control_prob: float = 0.25, seed: int = 0x63617272):
+    """The C5-like shape with every connection's one binary message cut over
+    `passes` passes of message_bytes / passes bytes each: a layout per pass."""
+    import numpy as np
+    from gev_amd import workloads
+    rng = np.random.default_rng(seed + passes)
+    per = message_bytes // passes
+    lays = []
+    for p in range(passes):
+        lengths, b0s, ms = [], [], []
+        for _ in range(n_conns):
+            L, B = [], []
+            left = per if p < passes - 1 else message_bytes - per * (passes - 1)
+            while left > 0:
+                f = int(min(left, rng.integers(1, max_fragment + 1)))
+                left -= f
+                L.append(f)
+                B.append((0x80 if left == 0 and p == passes - 1 else 0) | (0x2 if p == 0 and len(L) == 1 else 0))
+                if left > 0 and rng.random() < control_prob:
+                    L.append(int(rng.integers(0, 126)))
+                    B.append(0x80 | (0x9 if rng.random() < 0.5 else 0xA))
+            lengths.append(np.array(L, np.int64))
+            b0s.append(np.array(B, np.uint8))
+            ms.append(np.ones(len(L), np.uint8))
+        lays.append(workloads.assemble(f"C5-like, pass {p + 1} of {passes}", lengths, b0s, ms, seed + 97 * p))
+    return lays
+
+
+def bench_carry(eng, args):
+    """gevws_join_carry_async pass by pass for messages cut over 2, 4 and 16
+    passes: per pass the bytes the call moves (read + written, both sides), its
+    time, and the ratio to gevws_copy_async moving as many bytes."""
+    import numpy as np
+    import torch
+
+    import gev_amd
+    dev = torch.device("cuda", 0)
+    n_conns, message_bytes = 64, 1 << 20
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.reps
+
+    for k in (2, 4, 16):
+        state = torch.zeros((n_conns, 8), dtype=torch.uint8, device=dev)
+        carry = gev_amd.Carry(eng, n_conns, 2 * message_bytes)
+        want0 = b""
+        rows = []
+        for p, lay in enumerate(layouts_cut(k, n_conns, message_bytes)):
+            arena = torch.zeros(lay.arena_bytes + gev_amd.IN_PAD, dtype=torch.uint8, device=dev)
+            desc = torch.from_numpy(lay.desc.view(np.uint8).reshape(-1).copy()).to(dev)
+            out = eng.alloc_batch(n_conns, lay.n_frames, lay.payload_padded)
+            eng.synth(arena, desc, lay.n_frames, lay.seed)
+            eng.decode_async(arena, lay.arena_bytes, torch.from_numpy(lay.conns.copy()).to(dev), n_conns, out,
+                             lay.n_frames, lay.payload_padded)
+            torch.cuda.synchronize()
+            assert int(out.summary_host()["status"]) == 0 and int(out.summary_host()["frames"]) == lay.n_frames
+            msgs = eng.messages(out, state)
+            n = int(msgs.summary_host()["frames"])
+            assert n == n_conns and not msgs.conn_msg_host()["error"].any()
+            fr, co = out.frames_host(), out.conn_out_host()
+            for f in range(int(co["first_frame"][0]), int(co["first_frame"][0]) + int(co["nframes"][0])):
+                if not int(fr["opcode"][f]) & 8:  # connection 0's bytes, for the check behind the last pass
+                    o = int(fr["payload_off"][f])
+                    want0 += out.payload[o: o + int(fr["length"][f])].cpu().numpy().tobytes()
+            src_side, src_used = carry.side, carry.used
+            res = eng.join(out, msgs, flags=gev_amd.JOIN_ALL, carry=carry)  # sizes the arenas, checks, swaps
+            s, cs = res.summary_host(), res.carry_summary_host()
+            last = p == k - 1
+            assert int(s["frames"]) == (n_conns if last else 0) and int(cs["frames"]) == (0 if last else n_conns)
+            assert int(cs["errors"]) == 0
+            if last:
+                assert res.body_bytes(0) == want0 and len(want0) == message_bytes
+            else:
+                assert carry.carried_bytes(0) == want0
+            moved = sum(int(x["payload_len"]) + int(x["payload_bytes"]) for x in (s, cs))
+            copy_bytes = moved // 2 // 16 * 16
+            csrc = torch.empty(copy_bytes + 16, dtype=torch.uint8, device=dev)
+            cdst = torch.empty(copy_bytes + 16, dtype=torch.uint8, device=dev)
+            dst_side = 1 - src_side
+
+            def join():
+                eng.join_carry_async(out.frames, msgs.n_frames, msgs.messages, n, msgs.msg_of, msgs.summary,
+                                     out.payload, None, None, gev_amd.JOIN_ALL, res.bodies, res.out, res.out_cap,
+                                     res.summary, msgs.conn_msg, n_conns, carry.max_message_bytes,
+                                     carry.records[src_side], carry.arenas[src_side], src_used,
+                                     carry.records[dst_side], carry.arenas[dst_side], carry.cap(dst_side),
+                                     res.carry_summary)
+
+            def copy():
+                eng.copy_(cdst, csrc, copy_bytes)
+
+            for _ in range(args.warmup):
+                join(), copy()
+            torch.cuda.synchronize()
+            tj, tc = [], []
+            for _ in range(args.rounds):
+                tj.append(timed(join))
+                tc.append(timed(copy))
+            j, c = median(tj), median(tc)
+            rows.append({"pass": p + 1, "frames": lay.n_frames, "carried_in_bytes": src_used,
+                         "bytes_moved": moved, "join_ms": round(j, 4), "GBps": round(moved / j / 1e6, 1),
+                         "copy_ms": round(c, 4), "join_over_copy": round(j / c, 3)})
+            del arena, out, msgs, res, csrc, cdst
+            torch.cuda.empty_cache()
+        line = json.dumps({
+            "path": "join step with the carry (gevws_join_carry_async, JOIN_ALL), pass by pass",
+            "shape": f"C5-like: {n_conns} connections, one 1 MiB message each, fragments up to 64 KiB",
+            "passes": k, "message_bytes_moved_total": sum(r["bytes_moved"] for r in rows),
+            "moved_over_message_bytes": round(sum(r["bytes_moved"] for r in rows) / (n_conns * message_bytes), 2),
+            "rows": rows, "rounds": args.rounds, "reps": args.reps, "warmup": args.warmup})
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -63,6 +193,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="launches per timed window")
     ap.add_argument("--shapes", default="c5,small")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
+    ap.add_argument("--carry", action="store_true",
+                    help="instead of the shapes: the join with its carry, 1 MiB messages cut over 2, 4 and 16 passes")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -71,6 +203,10 @@ def main():
 
     dev = torch.device("cuda", 0)
     eng = gev_amd.Engine(0)
+    if args.carry:
+        bench_carry(eng, args)
+        eng.close()
+        return
     for shape in args.shapes.split(","):
         lay = SHAPES[shape]()
         n_frames, n_conns = lay.n_frames, lay.n_conns
