@@ -30,7 +30,7 @@ from ._abi import EXT_CLIENT_TAKEOVER, INF_CTX_BYTES, NEGOTIATE_CLIENT_TAKEOVER
 from ._abi import DEFLATE_DYNAMIC, DEFLATE_PLAIN_IF_NOT_SMALLER
 from ._abi import DEF_CTX_BYTES, EXT_SERVER_TAKEOVER, NEGOTIATE_SERVER_TAKEOVER
 from ._abi import BODY_INFLATED, BODY_JOINED, BODY_WHOLE, JOIN_ALL
-from ._abi import CARRY_LOST, CARRY_OPEN
+from ._abi import CARRY_COMPRESSED, CARRY_KEEP_COMPRESSED, CARRY_LOST, CARRY_OPEN
 from ._abi import HANDLER_ECHO_BINARY, HANDLER_ECHO_TEXT, HANDLER_NONE
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
@@ -342,12 +342,16 @@ class Carry:
     """The join step's carry between passes (Engine.join(carry=...)): every
     connection's open plain message, its record and its bytes so far, on the
     device.  Two sides that Engine.join swaps after each pass that succeeded:
-    `records` / `arena` hold the state behind the last pass."""
+    `records` / `arena` hold the state behind the last pass.  compressed: open
+    permessage-deflate messages are kept too, as compressed bytes
+    (CARRY_KEEP_COMPRESSED), for Engine.inflate(carry=...) to finish."""
 
-    def __init__(self, engine: "Engine", n_conns: int, max_message_bytes: int, arena_bytes: int = 0):
+    def __init__(self, engine: "Engine", n_conns: int, max_message_bytes: int, arena_bytes: int = 0,
+                 compressed: bool = False):
         torch = _torch()
         self.device = torch.device("cuda", engine.device)
         self.n_conns, self.max_message_bytes = n_conns, max_message_bytes
+        self.carry_flags = CARRY_KEEP_COMPRESSED if compressed else 0
         self.records = [torch.zeros((max(n_conns, 1), 32), dtype=torch.uint8, device=self.device) for _ in range(2)]
         self.arenas = [self._arena(arena_bytes) for _ in range(2)]
         self.used = 0     # bytes of `arena` the records point into
@@ -747,25 +751,55 @@ class Engine:
         if st != OK:
             raise RuntimeError(f"gevws_inflate_ctx_async: {status_string(st)}")
 
+    def inflate_carry_async(self, frames, max_frames: int, messages, max_messages: int, msg_of, msg_summary, payload,
+                            max_message_bytes: int, state, inflated, out, out_cap: int, summary, conn_ext, contexts,
+                            n_conns: int, carry_in, carry_src, carry_src_bytes: int, stream=None) -> None:
+        """gevws_inflate_carry_async: inflate_ctx_async plus the `in` side of
+        the join's carry (carry_in: uint8 [n_conns, 32] records, carry_src:
+        their arena) -- a continued compressed message whose record is
+        CARRY_OPEN | CARRY_COMPRESSED is inflated behind its carried bytes.
+        n_conns is required; conn_ext / contexts may be None.  carry_in or
+        carry_src None is inflate_ctx_async."""
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        st = lib.gevws_inflate_carry_async(
+            self._ctx, _stream_handle(stream), frames.data_ptr(), max_frames, messages.data_ptr(), max_messages,
+            msg_of.data_ptr(), msg_summary.data_ptr(), payload.data_ptr(), max_message_bytes, p(state),
+            inflated.data_ptr(), out.data_ptr(), out_cap, summary.data_ptr(), p(conn_ext), p(contexts), n_conns,
+            p(carry_in), p(carry_src), carry_src_bytes)
+        if st != OK:
+            raise RuntimeError(f"gevws_inflate_carry_async: {status_string(st)}")
+
     def inflate(self, out: "Batch", msgs: "Messages", max_message_bytes: int, state=None,
-                out_cap: Optional[int] = None, stream=None, conn_ext=None, contexts=None) -> "Inflated":
+                out_cap: Optional[int] = None, stream=None, conn_ext=None, contexts=None,
+                carry: Optional["Carry"] = None) -> "Inflated":
         """The inflate step behind Engine.messages(out, conn_ext=...): every
         whole compressed message of the pass inflated.  Grows the output once
         on ERR_CAPACITY (nothing is written and the state is untouched by the
         call that did not fit).  With conn_ext and contexts (uint8 [n_conns,
         INF_CTX_BYTES], the caller's, carried from pass to pass) connections
         with EXT_CLIENT_TAKEOVER keep their window between messages; the call
-        that did not fit leaves the contexts untouched too."""
+        that did not fit leaves the contexts untouched too.  With carry (a
+        Carry(compressed=True), before the pass's join) a compressed message
+        that began in an earlier pass and ends in this one is inflated behind
+        its carried bytes; the carry is only read."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n = int(msgs.summary_host()["frames"])
         if out_cap is None:
             out_cap = 4 * int(out.summary_host()["payload_bytes"]) + 16 * n
+            if carry is not None:
+                out_cap += 4 * carry.used
         for attempt in range(2):
             res = Inflated(inflated=torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=dev),
                            out=torch.empty(max(out_cap, 16), dtype=torch.uint8, device=dev),
                            summary=torch.zeros(64, dtype=torch.uint8, device=dev), n_messages=n)
-            if conn_ext is not None and contexts is not None:
+            if carry is not None:
+                with_ctx = conn_ext is not None and contexts is not None
+                self.inflate_carry_async(out.frames, msgs.n_frames, msgs.messages, n, msgs.msg_of, msgs.summary,
+                                         out.payload, max_message_bytes, state, res.inflated, res.out, out_cap,
+                                         res.summary, conn_ext if with_ctx else None, contexts if with_ctx else None,
+                                         carry.n_conns, carry.records_in, carry.arena, carry.used, stream)
+            elif conn_ext is not None and contexts is not None:
                 self.inflate_ctx_async(out.frames, msgs.n_frames, msgs.messages, n, msgs.msg_of, msgs.summary,
                                        out.payload, max_message_bytes, state, res.inflated, res.out, out_cap,
                                        res.summary, conn_ext, contexts, int(contexts.shape[0]), stream)
@@ -890,6 +924,25 @@ class Engine:
         if st != OK:
             raise RuntimeError(f"gevws_join_carry_async: {status_string(st)}")
 
+    def join_carry_ext_async(self, frames, max_frames: int, messages, max_messages: int, msg_of, msg_summary, payload,
+                             inflated, inflate_summary, flags: int, bodies, out, out_cap: int, summary, conn_msg,
+                             n_conns: int, max_message_bytes: int, carry_in, carry_src, carry_src_bytes: int,
+                             carry_out, carry_dst, carry_cap: int, carry_summary, carry_flags: int,
+                             stream=None) -> None:
+        """gevws_join_carry_ext_async: join_carry_async plus carry_flags --
+        with CARRY_KEEP_COMPRESSED open compressed messages are carried as
+        compressed bytes (records CARRY_OPEN | CARRY_COMPRESSED) and a
+        continued one that the inflate finished is delivered INFLATED.
+        carry_flags 0 is join_carry_async."""
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        st = lib.gevws_join_carry_ext_async(
+            self._ctx, _stream_handle(stream), p(frames), max_frames, p(messages), max_messages, p(msg_of),
+            p(msg_summary), p(payload), p(inflated), p(inflate_summary), flags, p(bodies), p(out), out_cap,
+            p(summary), p(conn_msg), n_conns, max_message_bytes, p(carry_in), p(carry_src), carry_src_bytes,
+            p(carry_out), p(carry_dst), carry_cap, p(carry_summary), carry_flags)
+        if st != OK:
+            raise RuntimeError(f"gevws_join_carry_ext_async: {status_string(st)}")
+
     def _join_with_carry(self, out: "Batch", msgs: "Messages", inflated, flags: int, out_cap: Optional[int], stream,
                          conn_msg, carry: "Carry") -> "Bodies":
         torch = _torch()
@@ -909,12 +962,16 @@ class Engine:
             res = Bodies(bodies=torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=dev), out=arena,
                          summary=torch.zeros(64, dtype=torch.uint8, device=dev), payload=out.payload, n_messages=n,
                          out_cap=out_cap, carry_summary=torch.zeros(64, dtype=torch.uint8, device=dev))
-            self.join_carry_async(out.frames, msgs.n_frames, msgs.messages, n, msgs.msg_of, msgs.summary, out.payload,
-                                  inflated.inflated if inflated is not None else None,
-                                  inflated.summary if inflated is not None else None, flags, res.bodies, arena,
-                                  out_cap, res.summary, conn_msg, carry.n_conns, carry.max_message_bytes,
-                                  carry.records[src], carry.arenas[src], carry.used, carry.records[dst],
-                                  carry.arenas[dst], carry.cap(dst), res.carry_summary, stream)
+            args = (out.frames, msgs.n_frames, msgs.messages, n, msgs.msg_of, msgs.summary, out.payload,
+                    inflated.inflated if inflated is not None else None,
+                    inflated.summary if inflated is not None else None, flags, res.bodies, arena,
+                    out_cap, res.summary, conn_msg, carry.n_conns, carry.max_message_bytes,
+                    carry.records[src], carry.arenas[src], carry.used, carry.records[dst],
+                    carry.arenas[dst], carry.cap(dst), res.carry_summary)
+            if carry.carry_flags:
+                self.join_carry_ext_async(*args, carry.carry_flags, stream)
+            else:
+                self.join_carry_async(*args, stream)
             torch.cuda.synchronize(self.device)
             s, cs = res.summary_host(), res.carry_summary_host()
             short = [x for x in (s, cs) if int(x["status"]) == ERR_CAPACITY]
@@ -940,7 +997,9 @@ class Engine:
         (nothing is written by the call that did not fit).  With `carry` (a
         Carry; conn_msg: the message pass's table, msgs.conn_msg by default) a
         plain message that spans passes is kept in the carry and delivered with
-        its FIN frame; the carry's sides are swapped after a call that succeeded."""
+        its FIN frame (a Carry(compressed=True): a compressed one too, inflated
+        by Engine.inflate(carry=...) before this call); the carry's sides are
+        swapped after a call that succeeded."""
         if carry is not None:
             return self._join_with_carry(out, msgs, inflated, flags, out_cap, stream,
                                          msgs.conn_msg if conn_msg is None else conn_msg, carry)
@@ -1700,4 +1759,5 @@ __all__ = ["Engine", "Batch", "Comm", "RingBuffer", "Connection", "Protocol", "H
            "ERR_NOT_UPGRADED", "IN_PAD", "PAYLOAD_ALIGN", "TILE", "SUMMARY_UNORDERED",
            "DEFLATE_MSG_DTYPE", "DEFLATE_PLAIN_IF_NOT_SMALLER", "DEFLATE_DYNAMIC", "Deflated", "deflate_raw", "deflate_bound",
            "deflate_raw_ctx", "deflate_negotiate_takeover", "DEF_CTX_BYTES", "EXT_SERVER_TAKEOVER",
-           "NEGOTIATE_SERVER_TAKEOVER", "Carry", "CARRY_DTYPE", "CARRY_OPEN", "CARRY_LOST"]
+           "NEGOTIATE_SERVER_TAKEOVER", "Carry", "CARRY_DTYPE", "CARRY_OPEN", "CARRY_LOST",
+           "CARRY_COMPRESSED", "CARRY_KEEP_COMPRESSED"]

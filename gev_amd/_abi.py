@@ -86,6 +86,8 @@ BODY_INFLATED = 4
 # the join's carry (gevws_join_carry_async): gevws_carry.flags
 CARRY_OPEN = 1
 CARRY_LOST = 2
+CARRY_COMPRESSED = 4  # beside CARRY_OPEN: the bytes are compressed payload (gevws_join_carry_ext_async)
+CARRY_KEEP_COMPRESSED = 1  # gevws_join_carry_ext_async carry_flags bit
 
 IN_PAD = 64
 MEM_DEFAULT, MEM_FINE, MEM_UNCACHED = 0, 1, 2  # gevws_device_alloc kinds
@@ -320,6 +322,13 @@ SIGNATURES = {
     "gevws_join_carry_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, P, P, P, P, P,
                                               ctypes.c_uint32, P, P, ctypes.c_uint64, P, P, ctypes.c_uint32,
                                               ctypes.c_uint64, P, P, ctypes.c_uint64, P, P, ctypes.c_uint64, P]),
+    "gevws_join_carry_ext_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, P, P, P, P, P,
+                                                  ctypes.c_uint32, P, P, ctypes.c_uint64, P, P, ctypes.c_uint32,
+                                                  ctypes.c_uint64, P, P, ctypes.c_uint64, P, P, ctypes.c_uint64, P,
+                                                  ctypes.c_uint32]),
+    "gevws_inflate_carry_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, P, P, P,
+                                                 ctypes.c_uint64, P, P, P, ctypes.c_uint64, P, P, P, ctypes.c_uint32,
+                                                 P, P, ctypes.c_uint64]),
     "gevws_reply_bodies_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, ctypes.c_int, P, P, ctypes.c_uint32,
                                                 P, P, P, P, P, P, P]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),

@@ -22,6 +22,11 @@
 // the connection's slot of d_inf_ctx (see "context takeover" below).  The
 // <false> instances are the kernels of gevws_inflate_async, unchanged.
 //
+// gevws_inflate_carry_async (compressed messages that span passes) launches the
+// <true, true> instances: a continued message whose connection's carry record
+// is OPEN | COMPRESSED is whole -- the carried bytes are one more fragment of
+// its source, in front of first_frame.  The instances above do not change.
+//
 // A wave's decode state -- bit buffer, counters, each Huffman code's limits --
 // is the same in every lane; the lanes differ only where bytes move: the 1 KiB
 // refills of the input (hopping from fragment to fragment), match copies,
@@ -69,7 +74,9 @@ inline InfScratch inf_scratch(void* base, uint64_t max_messages) {
 
 // ------------------------------------------------------------------ the source
 // S of message m: the payloads of its data frames, then 00 00 ff ff, through a
-// 1 KiB LDS buffer.  Reads hdr.length bytes of a frame and not one more.
+// 1 KiB LDS buffer.  Reads hdr.length bytes of a frame and not one more.  With
+// a carry, a continued message's carried bytes come first (prefix()): a run of
+// the carry arena that starts on 16, read up to its length and not one more.
 struct InfSource {
   const gevws_frame* __restrict__ fr;
   const int64_t* __restrict__ msg_of;
@@ -89,6 +96,10 @@ struct InfSource {
                        uint64_t m_, const gevws_message& msg, uint64_t max_frames_)
       : fr(fr_), msg_of(msg_of_), payload(payload_), inbuf(inbuf_), m(m_), f(msg.first_frame),
         max_frames(max_frames_), frames_left(msg.nframes), lane(threadIdx.x & 63) {}
+
+  // The carried bytes of a continued message: the open fragment before
+  // advance() first looks at first_frame (none of them: advance() at once).
+  __device__ __forceinline__ void prefix(const uint8_t* p_, uint64_t L_) { p = p_, L = L_, foff = 0; }
 
   // The buffer is empty and the fragment used up: opens the next fragment
   // with bytes, or puts the tail into the buffer; false at the end of S.
@@ -274,6 +285,53 @@ __device__ __forceinline__ bool inf_wanted(const gevws_message& msg) {
   return (msg.flags & all) == all;
 }
 
+// The carry of gevws_inflate_carry_async: the `in` side the pass's join reads
+// afterwards.  Only read here.
+struct InfCarry {
+  const gevws_carry* __restrict__ in;
+  const uint8_t* __restrict__ src;
+  uint64_t src_bytes;
+};
+// What the carry makes of a compressed message: both passes ask here, so they
+// decide alike.
+enum : uint32_t {
+  kInfPending = 0,  // not whole: GEVWS_INF_PENDING
+  kInfWhole = 1,    // BEGIN and END in the batch
+  kInfCarried = 2,  // continued, END here, the record OPEN | COMPRESSED: whole behind pre bytes at psrc
+  kInfLost = 3,     // continued, END here, the record LOST with a status: DONE with that status
+};
+struct InfWhole {
+  uint32_t kind, status;
+  uint64_t pre, psrc;
+};
+// An OPEN record the caller did not get from a join: never an address.
+__device__ __forceinline__ bool inf_carry_bad(const InfCarry& ca, uint32_t c) {
+  const gevws_carry ci = ca.in[c];
+  const uint64_t off = uniform64(ci.off), len = uniform64(ci.length);
+  return (uniform32(ci.flags) & GEVWS_CARRY_OPEN) && ((off & 15) || off > ca.src_bytes || len > ca.src_bytes - off);
+}
+// (msg.conn is below n_conns and its record passed inf_carry_bad)
+template <bool CARRY>
+__device__ __forceinline__ InfWhole inf_whole(const gevws_message& msg, const InfCarry& ca) {
+  InfWhole w;
+  w.kind = inf_wanted(msg) ? kInfWhole : kInfPending, w.status = 0, w.pre = w.psrc = 0;
+  if constexpr (CARRY) {
+    const uint32_t want = GEVWS_MSG_COMPRESSED | GEVWS_MSG_END;
+    if (w.kind == kInfWhole || (uniform32(msg.flags) & (want | GEVWS_MSG_BEGIN)) != want ||
+        uniform32(msg.status) != GEVWS_MSG_OK)
+      return w;
+    const gevws_carry ci = ca.in[uniform32(msg.conn)];
+    const uint32_t cf = uniform32(ci.flags);
+    const uint32_t open = GEVWS_CARRY_OPEN | GEVWS_CARRY_COMPRESSED;
+    if ((cf & open) == open) {
+      w.kind = kInfCarried, w.pre = uniform64(ci.length), w.psrc = uniform64(ci.off);
+    } else if (!(cf & GEVWS_CARRY_OPEN) && (cf & GEVWS_CARRY_LOST) && uniform32(ci.status)) {
+      w.kind = kInfLost, w.status = uniform32(ci.status);
+    }
+  }
+  return w;
+}
+
 // ------------------------------------------------------------------ context takeover
 // A takeover connection's compressed messages depend on each other in order
 // (message k's window is the output of the messages before it), so the wave of
@@ -321,13 +379,14 @@ __device__ __forceinline__ void inf_size_record(uint64_t k, const InfRec& r, uin
 // The sizing pass over connection c's messages from m on: needs no window
 // bytes, only the slot's head; the history length runs through the chain in
 // registers.  Writes the records, nothing to the slot.
+template <bool CARRY>
 __device__ __forceinline__ void inf_size_chain(const gevws_frame* __restrict__ fr, uint64_t max_frames,
                                                const gevws_message* __restrict__ msgs, uint64_t n, uint64_t m,
                                                uint32_t c, const int64_t* __restrict__ msg_of,
                                                const uint8_t* __restrict__ payload, uint64_t limit,
                                                const uint8_t* __restrict__ slot, uint8_t* s_in,
                                                gevws_inflate::Tables& s_tab, uint64_t* __restrict__ blk,
-                                               InfRec* __restrict__ rec) {
+                                               InfRec* __restrict__ rec, const InfCarry& ca) {
   const uint64_t total = uniform64(*reinterpret_cast<const uint64_t*>(slot));
   uint32_t hist = total < kInfWin ? (uint32_t)total : kInfWin;
   uint32_t broken = uniform32(slot[8]);
@@ -340,11 +399,16 @@ __device__ __forceinline__ void inf_size_chain(const gevws_frame* __restrict__ f
     r.len = 0, r.status = GEVWS_MSG_OK, r.flags = GEVWS_INF_PENDING, r.pad = 0;
     if (broken) {  // the context is lost: the first failure's status, nothing decoded
       r.status = (uint8_t)broken, r.flags = GEVWS_INF_DONE;
-    } else if (stopped || !inf_wanted(msg)) {
+    } else if (InfWhole w; stopped || (w = inf_whole<CARRY>(msg, ca)).kind == kInfPending) {
       stopped = true;  // not whole in the batch: the chain stops here
+    } else if (CARRY && w.kind == kInfLost) {  // its bytes were dropped on the way: the context goes with them
+      r.status = (uint8_t)w.status, r.flags = GEVWS_INF_DONE;
+      broken = w.status;
     } else {
       uint64_t len = 0;
       InfSizeIo io(fr, msg_of, payload, s_in, k, msg, max_frames);
+      if constexpr (CARRY)
+        if (w.kind == kInfCarried) io.prefix(ca.src + w.psrc, w.pre);  // the chain's first link
       r.status = (uint8_t)gevws_inflate::inflate(io, s_tab, limit, &len, hist);
       r.flags = GEVWS_INF_DONE;
       if (r.status != GEVWS_MSG_OK) {
@@ -360,8 +424,9 @@ __device__ __forceinline__ void inf_size_chain(const gevws_frame* __restrict__ f
 
 // ------------------------------------------------------------------ 1. sizes and verdicts
 // CTX: contexts are given (gevws_inflate_ctx_async); <false> is the kernel of
-// gevws_inflate_async.
-template <bool CTX>
+// gevws_inflate_async.  CARRY (with CTX): a carry is given
+// (gevws_inflate_carry_async), and conn_ext / inf_ctx may be null.
+template <bool CTX, bool CARRY = false>
 __global__ __launch_bounds__(kInfBlock) void k_inf_size(const gevws_frame* __restrict__ fr, uint64_t max_frames,
                                                         const gevws_message* __restrict__ msgs,
                                                         uint64_t max_messages, const int64_t* __restrict__ msg_of,
@@ -369,7 +434,9 @@ __global__ __launch_bounds__(kInfBlock) void k_inf_size(const gevws_frame* __res
                                                         const uint8_t* __restrict__ payload, uint64_t limit,
                                                         uint64_t* __restrict__ blk, InfRec* __restrict__ rec,
                                                         const uint8_t* __restrict__ conn_ext,
-                                                        const uint8_t* __restrict__ inf_ctx, uint32_t n_conns) {
+                                                        const uint8_t* __restrict__ inf_ctx, uint32_t n_conns,
+                                                        InfCarry ca) {
+  static_assert(CTX || !CARRY, "the carry's kernels check conn like the contexts'");
   __shared__ __attribute__((aligned(16))) uint8_t s_in[kInfIn];
   __shared__ gevws_inflate::Tables s_tab;
   const uint64_t m = inf_block_message<CTX>();
@@ -382,10 +449,16 @@ __global__ __launch_bounds__(kInfBlock) void k_inf_size(const gevws_frame* __res
       if (threadIdx.x == 0) blk[m * kBlkFields + 3] = kInfInvalid;
       return;
     }
-    if (uniform32(conn_ext[c]) & GEVWS_EXT_CLIENT_TAKEOVER) {  // wave-uniform
+    if constexpr (CARRY) {
+      if (inf_carry_bad(ca, c)) {  // never an address: GEVWS_ERR_INVALID too, the connection counted once
+        if (threadIdx.x == 0 && !(m && msgs[m - 1].conn == c)) blk[m * kBlkFields + 3] = kInfInvalid;
+        return;
+      }
+    }
+    if ((!CARRY || conn_ext) && (uniform32(conn_ext[c]) & GEVWS_EXT_CLIENT_TAKEOVER)) {  // wave-uniform
       if (m && uniform32(msgs[m - 1].conn) == c) return;  // the connection's first message walks its messages
-      inf_size_chain(fr, max_frames, msgs, n, m, c, msg_of, payload, limit,
-                     inf_ctx + (uint64_t)c * GEVWS_INF_CTX_BYTES, s_in, s_tab, blk, rec);
+      inf_size_chain<CARRY>(fr, max_frames, msgs, n, m, c, msg_of, payload, limit,
+                            inf_ctx + (uint64_t)c * GEVWS_INF_CTX_BYTES, s_in, s_tab, blk, rec, ca);
       return;
     }
   }
@@ -393,8 +466,13 @@ __global__ __launch_bounds__(kInfBlock) void k_inf_size(const gevws_frame* __res
   InfRec r;
   r.len = 0, r.status = GEVWS_MSG_OK, r.flags = GEVWS_INF_PENDING, r.pad = 0;
   uint64_t len = 0;
-  if (inf_wanted(msg)) {
+  const InfWhole w = inf_whole<CARRY>(msg, ca);
+  if (CARRY && w.kind == kInfLost) {
+    r.status = (uint8_t)w.status, r.flags = GEVWS_INF_DONE;
+  } else if (w.kind != kInfPending) {
     InfSizeIo io(fr, msg_of, payload, s_in, m, msg, max_frames);
+    if constexpr (CARRY)
+      if (w.kind == kInfCarried) io.prefix(ca.src + w.psrc, w.pre);
     r.status = (uint8_t)gevws_inflate::inflate(io, s_tab, limit, &len);
     r.flags = GEVWS_INF_DONE;
     if (r.status != GEVWS_MSG_OK) len = 0;
@@ -428,13 +506,15 @@ __global__ void k_inf_verdict(gevws_summary* __restrict__ sum) {
 // indices, the chain is decoded with the ring position running on across the
 // messages, and at the end the ring bytes this pass produced go back to the
 // slot with the head: the ring image in HBM already holds the older bytes.
+template <bool CARRY>
 __device__ __forceinline__ void inf_emit_chain(const gevws_frame* __restrict__ fr, uint64_t max_frames,
                                                const gevws_message* __restrict__ msgs, uint64_t n, uint64_t m,
                                                uint32_t c, const int64_t* __restrict__ msg_of,
                                                const uint8_t* __restrict__ payload,
                                                const uint64_t* __restrict__ blk, const InfRec* __restrict__ rec,
                                                uint8_t* slot, uint8_t* s_win, uint8_t* s_in,
-                                               gevws_inflate::Tables& s_tab, uint8_t* __restrict__ d_out) {
+                                               gevws_inflate::Tables& s_tab, uint8_t* __restrict__ d_out,
+                                               const InfCarry& ca) {
   const uint32_t lane = threadIdx.x & 63;
   // what the sizing pass decided for the chain
   bool any = false;
@@ -463,6 +543,10 @@ __device__ __forceinline__ void inf_emit_chain(const gevws_frame* __restrict__ f
       const gevws_message msg = msgs[k];
       InfEmitIo<true> io(fr, msg_of, payload, s_in, k, msg, max_frames, s_win,
                          d_out + uniform64(blk[k * kBlkFields + 1]), total);
+      if constexpr (CARRY) {  // (a continued message the sizing pass inflated: its record was OPEN | COMPRESSED)
+        const InfWhole w = inf_whole<CARRY>(msg, ca);
+        if (w.kind == kInfCarried) io.prefix(ca.src + w.psrc, w.pre);
+      }
       uint64_t len = 0;
       // the sized length is the limit: the wave never writes past the message's allotted bytes
       (void)gevws_inflate::inflate(io, s_tab, (uint64_t)len_k, &len, total < kInfWin ? (uint32_t)total : kInfWin);
@@ -488,7 +572,7 @@ __device__ __forceinline__ void inf_emit_chain(const gevws_frame* __restrict__ f
 }
 
 // ------------------------------------------------------------------ 2. the bytes
-template <bool CTX>
+template <bool CTX, bool CARRY = false>
 __global__ __launch_bounds__(kInfBlock) void k_inf_emit(const gevws_frame* __restrict__ fr, uint64_t max_frames,
                                                         const gevws_message* __restrict__ msgs,
                                                         uint64_t max_messages, const int64_t* __restrict__ msg_of,
@@ -499,7 +583,8 @@ __global__ __launch_bounds__(kInfBlock) void k_inf_emit(const gevws_frame* __res
                                                         const gevws_summary* __restrict__ sum,
                                                         gevws_inflated* __restrict__ inflated,
                                                         uint8_t* __restrict__ d_out,
-                                                        const uint8_t* __restrict__ conn_ext, uint8_t* inf_ctx) {
+                                                        const uint8_t* __restrict__ conn_ext, uint8_t* inf_ctx,
+                                                        InfCarry ca) {
   __shared__ __attribute__((aligned(16))) uint8_t s_win[kInfWin];
   __shared__ __attribute__((aligned(16))) uint8_t s_in[kInfIn];
   __shared__ gevws_inflate::Tables s_tab;
@@ -522,16 +607,20 @@ __global__ __launch_bounds__(kInfBlock) void k_inf_emit(const gevws_frame* __res
   }
   if constexpr (CTX) {
     const uint32_t c = uniform32(msgs[m].conn);  // (below n_conns, or the summary were INVALID)
-    if (uniform32(conn_ext[c]) & GEVWS_EXT_CLIENT_TAKEOVER) {  // wave-uniform
+    if ((!CARRY || conn_ext) && (uniform32(conn_ext[c]) & GEVWS_EXT_CLIENT_TAKEOVER)) {  // wave-uniform
       if (m && uniform32(msgs[m - 1].conn) == c) return;  // the connection's first message walks its messages
-      inf_emit_chain(fr, max_frames, msgs, n, m, c, msg_of, payload, blk, rec,
-                     inf_ctx + (uint64_t)c * GEVWS_INF_CTX_BYTES, s_win, s_in, s_tab, d_out);
+      inf_emit_chain<CARRY>(fr, max_frames, msgs, n, m, c, msg_of, payload, blk, rec,
+                            inf_ctx + (uint64_t)c * GEVWS_INF_CTX_BYTES, s_win, s_in, s_tab, d_out, ca);
       return;
     }
   }
   if (r.flags != GEVWS_INF_DONE || r.status != GEVWS_MSG_OK || r.len == 0) return;
   const gevws_message msg = msgs[m];
   InfEmitIo<false> io(fr, msg_of, payload, s_in, m, msg, max_frames, s_win, d_out + base);
+  if constexpr (CARRY) {  // (a continued message the sizing pass inflated: its record was OPEN | COMPRESSED)
+    const InfWhole w = inf_whole<CARRY>(msg, ca);
+    if (w.kind == kInfCarried) io.prefix(ca.src + w.psrc, w.pre);
+  }
   uint64_t len = 0;
   // the sized length is the limit: the wave never writes past its allotted bytes
   (void)gevws_inflate::inflate(io, s_tab, (uint64_t)r.len, &len);
@@ -594,15 +683,19 @@ __global__ __launch_bounds__(kWalkBlock) void k_inf_state(const gevws_message* _
 
 using namespace gevws_impl;
 
-extern "C" int gevws_inflate_ctx_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames,
-                                       uint64_t max_frames, const gevws_message* d_messages, uint64_t max_messages,
-                                       const int64_t* d_msg_of, const gevws_summary* d_msg_summary,
-                                       const uint8_t* d_payload, uint64_t max_message_bytes, gevws_msg_state* d_state,
-                                       gevws_inflated* d_inflated, uint8_t* d_out, uint64_t out_cap,
-                                       gevws_summary* d_summary, const uint8_t* d_conn_ext, uint8_t* d_inf_ctx,
-                                       uint32_t n_conns) {
+extern "C" int gevws_inflate_carry_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames,
+                                         uint64_t max_frames, const gevws_message* d_messages, uint64_t max_messages,
+                                         const int64_t* d_msg_of, const gevws_summary* d_msg_summary,
+                                         const uint8_t* d_payload, uint64_t max_message_bytes,
+                                         gevws_msg_state* d_state, gevws_inflated* d_inflated, uint8_t* d_out,
+                                         uint64_t out_cap, gevws_summary* d_summary, const uint8_t* d_conn_ext,
+                                         uint8_t* d_inf_ctx, uint32_t n_conns, const gevws_carry* d_carry_in,
+                                         const uint8_t* d_carry_src, uint64_t carry_src_bytes) {
   const bool with_ctx = d_conn_ext && d_inf_ctx;  // either NULL: gevws_inflate_async, bit for bit
+  const bool with_carry = d_carry_in && d_carry_src;  // either NULL: gevws_inflate_ctx_async, bit for bit
   if (with_ctx && ((reinterpret_cast<uintptr_t>(d_inf_ctx) & 15) || max_messages > 0x7FF00000ull))
+    return GEVWS_ERR_INVALID;
+  if (with_carry && ((reinterpret_cast<uintptr_t>(d_carry_src) & 15) || max_messages > 0x7FF00000ull))
     return GEVWS_ERR_INVALID;
   if (!ctx || !d_summary || max_messages > 0x7FFFFFFFull || max_message_bytes < 1 ||
       max_message_bytes > 0xFFFFFFFFull)
@@ -623,24 +716,37 @@ extern "C" int gevws_inflate_ctx_async(gevws_ctx* ctx, void* stream, const gevws
   GEVWS_HIP(hipMemsetAsync(ctx->scratch, 0, s.total, st));
   const uint32_t nm = (uint32_t)max_messages;
   const uint32_t ng = kInfSpread * inf_grid_q(nm);  // the grid with contexts (inf_block_message)
-  if (with_ctx)
+  const InfCarry none{nullptr, nullptr, 0};
+  const InfCarry ca{d_carry_in, d_carry_src, carry_src_bytes};
+  const uint8_t* ext = with_ctx ? d_conn_ext : nullptr;  // (the carry's kernels take the contexts or none)
+  uint8_t* slots = with_ctx ? d_inf_ctx : nullptr;
+  if (with_carry)
+    k_inf_size<true, true><<<ng, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of,
+                                                     d_msg_summary, d_payload, max_message_bytes, s.blk, s.rec, ext,
+                                                     slots, n_conns, ca);
+  else if (with_ctx)
     k_inf_size<true><<<ng, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of,
                                                d_msg_summary, d_payload, max_message_bytes, s.blk, s.rec, d_conn_ext,
-                                               d_inf_ctx, n_conns);
+                                               d_inf_ctx, n_conns, none);
   else
     k_inf_size<false><<<nm, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of,
                                                 d_msg_summary, d_payload, max_message_bytes, s.blk, s.rec, nullptr,
-                                                nullptr, 0);
+                                                nullptr, 0, none);
   k_scan_blocks<false><<<1, kScanBlock, 0, st>>>(s.blk, nm, UINT64_MAX, out_cap, d_summary);
-  if (with_ctx) {
+  if (with_carry) {
+    k_inf_verdict<<<1, 1, 0, st>>>(d_summary);
+    k_inf_emit<true, true><<<ng, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of,
+                                                     d_msg_summary, d_payload, s.blk, s.rec, d_summary, d_inflated,
+                                                     d_out, ext, slots, ca);
+  } else if (with_ctx) {
     k_inf_verdict<<<1, 1, 0, st>>>(d_summary);
     k_inf_emit<true><<<ng, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of,
                                                d_msg_summary, d_payload, s.blk, s.rec, d_summary, d_inflated, d_out,
-                                               d_conn_ext, d_inf_ctx);
+                                               d_conn_ext, d_inf_ctx, none);
   } else {
     k_inf_emit<false><<<nm, kInfBlock, 0, st>>>(d_frames, max_frames, d_messages, max_messages, d_msg_of,
                                                 d_msg_summary, d_payload, s.blk, s.rec, d_summary, d_inflated, d_out,
-                                                nullptr, nullptr);
+                                                nullptr, nullptr, none);
   }
   k_inf_utf8<<<(nm + kWalkBlock / 64 - 1) / (kWalkBlock / 64), kWalkBlock, 0, st>>>(d_messages, max_messages,
                                                                                    d_msg_summary, d_summary,
@@ -650,6 +756,18 @@ extern "C" int gevws_inflate_ctx_async(gevws_ctx* ctx, void* stream, const gevws
                                                                            d_summary, d_inflated, d_state);
   GEVWS_HIP(hipGetLastError());
   return mark_last(ctx, st);
+}
+
+extern "C" int gevws_inflate_ctx_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames,
+                                       uint64_t max_frames, const gevws_message* d_messages, uint64_t max_messages,
+                                       const int64_t* d_msg_of, const gevws_summary* d_msg_summary,
+                                       const uint8_t* d_payload, uint64_t max_message_bytes, gevws_msg_state* d_state,
+                                       gevws_inflated* d_inflated, uint8_t* d_out, uint64_t out_cap,
+                                       gevws_summary* d_summary, const uint8_t* d_conn_ext, uint8_t* d_inf_ctx,
+                                       uint32_t n_conns) {
+  return gevws_inflate_carry_async(ctx, stream, d_frames, max_frames, d_messages, max_messages, d_msg_of,
+                                   d_msg_summary, d_payload, max_message_bytes, d_state, d_inflated, d_out, out_cap,
+                                   d_summary, d_conn_ext, d_inf_ctx, n_conns, nullptr, nullptr, 0);
 }
 
 extern "C" int gevws_inflate_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames, uint64_t max_frames,

@@ -20,7 +20,7 @@
 // Only k_join_copy touches payload bytes: L read, L rounded up to 16 written a
 // copied body.
 //
-// The carry (gevws_join_carry_async): the same four launches once more over
+// The carry (gevws_join_carry_async, gevws_join_carry_ext_async): the same four launches once more over
 // the connections instead of the messages -- k_carry_size / k_scan_blocks /
 // k_carry_place, then k_join_copy over the carry's tables into d_carry_dst --
 // and k_carry_verdict between the scans and the place passes.  The kernels of
@@ -140,17 +140,31 @@ struct JoinCarryIn {
   const gevws_carry* __restrict__ carry_in;  // may be null
   uint32_t n_conns;
   uint64_t max_bytes;
+  uint32_t carry_flags;  // GEVWS_CARRY_KEEP_COMPRESSED (gevws_join_carry_ext_async), or 0
 };
 // join_decide with the connection's carry: a continued message that ends here
-// is delivered behind its carried bytes (pre / psrc: where they are).
+// is delivered behind its carried bytes (pre / psrc: where they are).  With
+// KEEP_COMPRESSED a continued compressed message that ends here is the
+// inflate's: delivered where its record says, nothing of it copied.
 __device__ __forceinline__ JoinDec join_decide_carry(const gevws_message& m,
                                                      const gevws_inflated* __restrict__ inflated, uint64_t idx,
                                                      uint32_t call_flags, const JoinCarryIn& ca, uint64_t& pre,
                                                      uint64_t& psrc) {
   JoinDec d = join_decide(m, inflated, idx, call_flags);
   pre = psrc = 0;
+  const bool keep = ca.carry_flags & GEVWS_CARRY_KEEP_COMPRESSED;
+  if (keep && inflated && (m.flags & (GEVWS_MSG_BEGIN | GEVWS_MSG_COMPRESSED | GEVWS_MSG_END)) ==
+                              (GEVWS_MSG_COMPRESSED | GEVWS_MSG_END)) {
+    const gevws_inflated r = inflated[idx];  // (d.status is r.status already)
+    if ((r.flags & GEVWS_INF_DONE) && r.status == GEVWS_MSG_OK) {
+      d.flags = GEVWS_BODY_WHOLE | GEVWS_BODY_INFLATED;
+      d.length = r.length, d.inf_off = r.out_off;
+    }
+    return d;
+  }
   if ((m.flags & (GEVWS_MSG_BEGIN | GEVWS_MSG_COMPRESSED)) || !ca.carry_in || m.conn >= ca.n_conns) return d;
   const gevws_carry ci = ca.carry_in[m.conn];
+  if (keep && (ci.flags & GEVWS_CARRY_OPEN) && (ci.flags & GEVWS_CARRY_COMPRESSED)) return d;  // not this message's
   if (ci.flags & GEVWS_CARRY_OPEN) {
     if ((m.flags & GEVWS_MSG_END) && m.status == GEVWS_MSG_OK) {
       const uint64_t total = ci.length + m.length;
@@ -536,8 +550,12 @@ struct CarryIn {
   const gevws_carry* __restrict__ carry_in;  // may be null
   uint64_t carry_src_bytes, max_bytes;
   uint32_t n_conns;
+  uint32_t carry_flags;  // GEVWS_CARRY_KEEP_COMPRESSED, or 0
 };
 // n: the gated message count.  Nothing is indexed by a field before it is checked.
+// With KEEP_COMPRESSED an open compressed message is kept like a plain one,
+// its record marked COMPRESSED; a record and a message that disagree in that
+// bit (the caller mixed up its states) end LOST.
 __device__ __forceinline__ CarryDec carry_decide(const CarryIn& in, uint32_t c, uint64_t n) {
   CarryDec d;
   memset(&d, 0, sizeof(d));
@@ -552,17 +570,19 @@ __device__ __forceinline__ CarryDec carry_decide(const CarryIn& in, uint32_t c, 
   else if (cm.first_message > n || cm.nmessages > n - cm.first_message)
     d.invalid = true;
   if (d.invalid) return d;
+  const bool keep = in.carry_flags & GEVWS_CARRY_KEEP_COMPRESSED;
+  const uint8_t ci_comp = keep ? (ci.flags & GEVWS_CARRY_COMPRESSED) : 0;  // (without the flag the bit is not looked at)
   if (cm.nmessages) {  // the body side's verdict on a continued message that ends here
     const gevws_message f = in.msgs[cm.first_message];
     if (!(f.flags & (GEVWS_MSG_BEGIN | GEVWS_MSG_COMPRESSED)) && (f.flags & GEVWS_MSG_END) &&
-        f.status == GEVWS_MSG_OK && (ci.flags & GEVWS_CARRY_OPEN) &&
+        f.status == GEVWS_MSG_OK && (ci.flags & GEVWS_CARRY_OPEN) && !ci_comp &&
         (ci.length + f.length < ci.length || ci.length + f.length > in.max_bytes))
       d.too_big = 1;
   }
   if (cm.error != 0) return d;  // the carry is dropped
   if (cm.nmessages == 0) {      // the record moves forward
     if (ci.flags & GEVWS_CARRY_OPEN) {
-      d.flags = GEVWS_CARRY_OPEN, d.opcode = ci.opcode;
+      d.flags = GEVWS_CARRY_OPEN | ci_comp, d.opcode = ci.opcode;
       d.length = d.pre = ci.length, d.psrc = ci.off;
     } else if (ci.flags & GEVWS_CARRY_LOST) {
       d.flags = GEVWS_CARRY_LOST, d.opcode = ci.opcode, d.status = ci.status;
@@ -573,13 +593,16 @@ __device__ __forceinline__ CarryDec carry_decide(const CarryIn& in, uint32_t c, 
     if (l.flags & GEVWS_MSG_END) return d;
     d.opcode = l.opcode;
     const bool begin = l.flags & GEVWS_MSG_BEGIN;
-    if (l.flags & GEVWS_MSG_COMPRESSED) {
+    const uint8_t comp = keep && (l.flags & GEVWS_MSG_COMPRESSED) ? GEVWS_CARRY_COMPRESSED : 0;
+    if ((l.flags & GEVWS_MSG_COMPRESSED) && !keep) {
       d.flags = GEVWS_CARRY_LOST;
       d.status = !begin && (ci.flags & GEVWS_CARRY_LOST) ? ci.status : 0;
     } else if (begin) {
-      d.flags = GEVWS_CARRY_OPEN, d.length = l.length, d.msg = (int64_t)li;
+      d.flags = GEVWS_CARRY_OPEN | comp, d.length = l.length, d.msg = (int64_t)li;
+    } else if ((ci.flags & GEVWS_CARRY_OPEN) && comp != ci_comp) {
+      d.flags = GEVWS_CARRY_LOST;  // status 0
     } else if (ci.flags & GEVWS_CARRY_OPEN) {
-      d.flags = GEVWS_CARRY_OPEN, d.pre = ci.length, d.psrc = ci.off, d.msg = (int64_t)li;
+      d.flags = GEVWS_CARRY_OPEN | comp, d.pre = ci.length, d.psrc = ci.off, d.msg = (int64_t)li;
       d.length = ci.length + l.length;
       if (d.length < ci.length) d.length = UINT64_MAX;  // (over any limit)
     } else {
@@ -820,7 +843,7 @@ static int join_with_carry(gevws_ctx* ctx, hipStream_t st, const gevws_frame* d_
                            const gevws_conn_msg* d_conn_msg, uint32_t n_conns, uint64_t max_message_bytes,
                            const gevws_carry* d_carry_in, const uint8_t* d_carry_src, uint64_t carry_src_bytes,
                            gevws_carry* d_carry_out, uint8_t* d_carry_dst, uint64_t carry_cap,
-                           gevws_summary* d_carry_summary) {
+                           gevws_summary* d_carry_summary, uint32_t carry_flags) {
   if (max_message_bytes == 0 || max_message_bytes > 0xFFFFFFFFull || (reinterpret_cast<uintptr_t>(d_carry_dst) & 15) ||
       (reinterpret_cast<uintptr_t>(d_carry_src) & 15) || (d_carry_in && carry_src_bytes && !d_carry_src))
     return GEVWS_ERR_INVALID;
@@ -840,8 +863,8 @@ static int join_with_carry(gevws_ctx* ctx, hipStream_t st, const gevws_frame* d_
   r = ensure_scratch(ctx, join_scratch(nullptr, max_frames, max_messages, nblk, out_cap, n_conns, nblkc, carry_cap).total);
   if (r != GEVWS_OK) return r;
   const JoinScratch s = join_scratch(ctx->scratch, max_frames, max_messages, nblk, out_cap, n_conns, nblkc, carry_cap);
-  const JoinCarryIn ca{d_carry_in, n_conns, max_message_bytes};
-  const CarryIn in{d_messages, d_conn_msg, d_carry_in, carry_src_bytes, max_message_bytes, n_conns};
+  const JoinCarryIn ca{d_carry_in, n_conns, max_message_bytes, carry_flags};
+  const CarryIn in{d_messages, d_conn_msg, d_carry_in, carry_src_bytes, max_message_bytes, n_conns, carry_flags};
   const uint32_t grid = (uint32_t)ctx->num_cus * kJoinWgPerCU;
   GEVWS_HIP(hipMemsetAsync(s.ctl, 0, s.zero_bytes, st));
   if (max_messages) {
@@ -872,16 +895,19 @@ static int join_with_carry(gevws_ctx* ctx, hipStream_t st, const gevws_frame* d_
   return mark_last(ctx, st);
 }
 
-extern "C" int gevws_join_carry_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames, uint64_t max_frames,
-                                      const gevws_message* d_messages, uint64_t max_messages, const int64_t* d_msg_of,
-                                      const gevws_summary* d_msg_summary, const uint8_t* d_payload,
-                                      const gevws_inflated* d_inflated, const gevws_summary* d_inflate_summary,
-                                      uint32_t flags, gevws_body* d_bodies, uint8_t* d_out, uint64_t out_cap,
-                                      gevws_summary* d_summary, const gevws_conn_msg* d_conn_msg, uint32_t n_conns,
-                                      uint64_t max_message_bytes, const gevws_carry* d_carry_in,
-                                      const uint8_t* d_carry_src, uint64_t carry_src_bytes, gevws_carry* d_carry_out,
-                                      uint8_t* d_carry_dst, uint64_t carry_cap, gevws_summary* d_carry_summary) {
-  if (!ctx || !d_summary || (flags & ~GEVWS_JOIN_ALL) || max_frames > 0xFFFFFFFFull ||
+extern "C" int gevws_join_carry_ext_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames,
+                                          uint64_t max_frames, const gevws_message* d_messages, uint64_t max_messages,
+                                          const int64_t* d_msg_of, const gevws_summary* d_msg_summary,
+                                          const uint8_t* d_payload, const gevws_inflated* d_inflated,
+                                          const gevws_summary* d_inflate_summary, uint32_t flags,
+                                          gevws_body* d_bodies, uint8_t* d_out, uint64_t out_cap,
+                                          gevws_summary* d_summary, const gevws_conn_msg* d_conn_msg,
+                                          uint32_t n_conns, uint64_t max_message_bytes,
+                                          const gevws_carry* d_carry_in, const uint8_t* d_carry_src,
+                                          uint64_t carry_src_bytes, gevws_carry* d_carry_out, uint8_t* d_carry_dst,
+                                          uint64_t carry_cap, gevws_summary* d_carry_summary, uint32_t carry_flags) {
+  if (!ctx || !d_summary || (flags & ~GEVWS_JOIN_ALL) || (carry_flags & ~GEVWS_CARRY_KEEP_COMPRESSED) ||
+      max_frames > 0xFFFFFFFFull ||
       max_messages > 0x7FFFFFFFull * kWalkBlock)
     return GEVWS_ERR_INVALID;
   DeviceGuard g(ctx->device);
@@ -890,7 +916,7 @@ extern "C" int gevws_join_carry_async(gevws_ctx* ctx, void* stream, const gevws_
     return join_with_carry(ctx, st, d_frames, max_frames, d_messages, max_messages, d_msg_of, d_msg_summary, d_payload,
                            d_inflated, d_inflate_summary, flags, d_bodies, d_out, out_cap, d_summary, d_conn_msg,
                            n_conns, max_message_bytes, d_carry_in, d_carry_src, carry_src_bytes, d_carry_out,
-                           d_carry_dst, carry_cap, d_carry_summary);
+                           d_carry_dst, carry_cap, d_carry_summary, carry_flags);
   // the NULL call: gevws_join_async
   if (max_messages == 0) {
     GEVWS_HIP(hipMemsetAsync(d_summary, 0, sizeof(gevws_summary), st));
@@ -907,7 +933,7 @@ extern "C" int gevws_join_carry_async(gevws_ctx* ctx, void* stream, const gevws_
   if (r != GEVWS_OK) return r;
   const JoinScratch s = join_scratch(ctx->scratch, max_frames, max_messages, nblk, out_cap);
   GEVWS_HIP(hipMemsetAsync(s.ctl, 0, s.zero_bytes, st));
-  const JoinCarryIn none{nullptr, 0, 0};
+  const JoinCarryIn none{nullptr, 0, 0, 0};
   k_join_size<false><<<nblk, kWalkBlock, 0, st>>>(d_messages, max_messages, d_msg_summary, d_inflated,
                                                   d_inflate_summary, flags, s.ctl, s.blk, none);
   k_scan_blocks<false><<<1, kScanBlock, 0, st>>>(s.blk, nblk + 1, UINT64_MAX, out_cap, d_summary);
@@ -919,6 +945,22 @@ extern "C" int gevws_join_carry_async(gevws_ctx* ctx, void* stream, const gevws_
       d_out, nullptr, nullptr, nullptr, 0);
   GEVWS_HIP(hipGetLastError());
   return mark_last(ctx, st);
+}
+
+extern "C" int gevws_join_carry_async(gevws_ctx* ctx, void* stream, const gevws_frame* d_frames, uint64_t max_frames,
+                                      const gevws_message* d_messages, uint64_t max_messages, const int64_t* d_msg_of,
+                                      const gevws_summary* d_msg_summary, const uint8_t* d_payload,
+                                      const gevws_inflated* d_inflated, const gevws_summary* d_inflate_summary,
+                                      uint32_t flags, gevws_body* d_bodies, uint8_t* d_out, uint64_t out_cap,
+                                      gevws_summary* d_summary, const gevws_conn_msg* d_conn_msg, uint32_t n_conns,
+                                      uint64_t max_message_bytes, const gevws_carry* d_carry_in,
+                                      const uint8_t* d_carry_src, uint64_t carry_src_bytes, gevws_carry* d_carry_out,
+                                      uint8_t* d_carry_dst, uint64_t carry_cap, gevws_summary* d_carry_summary) {
+  return gevws_join_carry_ext_async(ctx, stream, d_frames, max_frames, d_messages, max_messages, d_msg_of,
+                                    d_msg_summary, d_payload, d_inflated, d_inflate_summary, flags, d_bodies, d_out,
+                                    out_cap, d_summary, d_conn_msg, n_conns, max_message_bytes, d_carry_in,
+                                    d_carry_src, carry_src_bytes, d_carry_out, d_carry_dst, carry_cap, d_carry_summary,
+                                    0);
 }
 
 extern "C" int gevws_reply_bodies_async(gevws_ctx* ctx, void* stream, const gevws_body* d_bodies,

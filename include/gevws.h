@@ -603,7 +603,7 @@ int gevws_inflate_raw(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap,
  * connection, kept between messages and between passes.  Additions to ABI
  * version 3: nothing above changes.  (The outbound direction keeps
  * server_no_context_takeover; a compressed message that spans two passes is
- * still GEVWS_INF_PENDING.)
+ * GEVWS_INF_PENDING here and whole in gevws_inflate_carry_async.)
  *
  * GEVWS_EXT_CLIENT_TAKEOVER is a second bit of the d_conn_ext byte, set beside
  * GEVWS_EXT_DEFLATE for a connection whose client may keep its LZ77 window
@@ -1018,8 +1018,7 @@ int gevws_join_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_frames, 
  *     LOST with status GEVWS_MSG_ERR_TOO_BIG instead.  A compressed message
  *     that began in this batch becomes LOST with status 0; a continuation of a
  *     LOST ci becomes LOST with ci.status, of a zero ci LOST with status 0.
- *     (Compressed messages that span passes stay GEVWS_INF_PENDING in the
- *     inflate: out of scope.)
+ *     (gevws_join_carry_ext_async below keeps them instead.)
  *   - No message in this batch (nmessages == 0: idle, control frames only,
  *     decode status < 0): the record moves forward unchanged in meaning -- an
  *     OPEN one's bytes are copied to d_carry_dst (the limit applies), a LOST
@@ -1060,7 +1059,7 @@ int gevws_join_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_frames, 
  * nothing else is written.  max_message_bytes outside 1 .. 2^32 - 1, an
  * unknown flag bit, or an arena off its 16-byte boundary is GEVWS_ERR_INVALID
  * from the call. */
-#define GEVWS_CARRY_OPEN 1u   /* off / length: the open plain message's bytes so far */
+#define GEVWS_CARRY_OPEN 1u   /* off / length: the open message's bytes so far (plain, unless COMPRESSED below) */
 #define GEVWS_CARRY_LOST 2u   /* a message is open but its bytes are not kept; status says why */
 typedef struct gevws_carry {  /* 32 bytes per connection; all-zero = no message open */
     uint64_t off;      /* into the carry arena, on GEVWS_PAYLOAD_ALIGN */
@@ -1082,6 +1081,103 @@ int gevws_join_carry_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_fr
                            const uint8_t *d_carry_src, uint64_t carry_src_bytes,
                            gevws_carry *d_carry_out, uint8_t *d_carry_dst, uint64_t carry_cap,
                            gevws_summary *d_carry_summary);
+
+/* Compressed messages that span passes: the carry keeps an open
+ * permessage-deflate message's compressed bytes, and the inflate of the pass
+ * that holds its FIN frame reads them as the front of its stream.  Nothing of
+ * the decoder's state survives a pass.  Additions to ABI version 3: nothing
+ * above changes.
+ *
+ * GEVWS_CARRY_COMPRESSED is a third bit of gevws_carry.flags, set beside
+ * GEVWS_CARRY_OPEN: off / length are then the compressed payload bytes so far
+ * (the tail 00 00 ff ff is never stored).  GEVWS_CARRY_KEEP_COMPRESSED is a bit
+ * of carry_flags.
+ *
+ * gevws_join_carry_ext_async is gevws_join_carry_async plus carry_flags, and
+ * gevws_join_carry_async is its carry_flags == 0 call, bit for bit (the
+ * COMPRESSED bit of an input record is then not looked at).  Any other bit of
+ * carry_flags is GEVWS_ERR_INVALID from the call; the bits of `flags` stay as
+ * they are.  With GEVWS_CARRY_KEEP_COMPRESSED:
+ *
+ * d_carry_out[c] (carry side), where the connection's last message has
+ * GEVWS_MSG_COMPRESSED and no END:
+ *   - it began in this batch: OPEN | COMPRESSED with its data frames' bytes;
+ *   - it continues an OPEN | COMPRESSED ci: OPEN | COMPRESSED with the carried
+ *     bytes followed by this batch's fragments;
+ *   - it continues a zero or LOST ci: LOST, as above;
+ *   - it continues an OPEN ci without COMPRESSED (the caller mixed up its
+ *     states): LOST with status 0.  So does a plain message without END that
+ *     continues an OPEN | COMPRESSED ci.
+ * max_message_bytes bounds the compressed bytes kept: over it the record is
+ * LOST with GEVWS_MSG_ERR_TOO_BIG and counted in d_carry_summary.errors, like
+ * a plain message.  The idle forward (nmessages == 0) keeps the bit and copies
+ * the bytes.
+ *
+ * Continued message (body side).  A message with COMPRESSED and END and
+ * without BEGIN is delivered WHOLE | INFLATED exactly when d_inflated[m] has
+ * GEVWS_INF_DONE and status OK (gevws_inflate_carry_async below); off and
+ * length are the inflate record's.  Otherwise it is undelivered with the
+ * inflate record's status (without d_inflated: the message's).  The join
+ * copies nothing of it.  A plain continued message over an OPEN | COMPRESSED
+ * ci is undelivered, as over a zero one.
+ *
+ * Everything else -- layout, summaries, capacity, gates, malformed input -- is
+ * as above, with the new bit allowed in an input record.
+ *
+ * gevws_inflate_carry_async is gevws_inflate_ctx_async plus d_carry_in,
+ * d_carry_src and carry_src_bytes: the same `in` side the pass's join reads
+ * afterwards.  The inflate only reads it.  With d_carry_in or d_carry_src NULL
+ * it is gevws_inflate_ctx_async bit for bit (which is that NULL call).
+ * Otherwise n_conns is required, with or without contexts (d_conn_ext or
+ * d_inf_ctx NULL: no connection has takeover), and with ci =
+ * d_carry_in[msg.conn] a compressed message without BEGIN, with END and with
+ * message status OK is:
+ *   - ci OPEN | COMPRESSED: whole.  Its stream S is the ci.length carried
+ *     bytes, then its data frames' bytes as above, then 00 00 ff ff.  Verdict,
+ *     bytes, max_message_bytes (which bounds the inflated output), the UTF-8
+ *     pass, d_state.failed and the summary are what one pass that holds the
+ *     whole message gives.  On a takeover connection it is the first link of
+ *     the chain and the chain goes on behind it, so a slot stays a function of
+ *     the connection's stream alone, for cuts inside a message too.
+ *   - ci LOST with a nonzero status: GEVWS_INF_DONE, that status, length 0.  It
+ *     takes no space and counts in `errors`; on a takeover connection it loses
+ *     the context, as a failed message does.
+ *   - anything else (ci zero, LOST with status 0, OPEN without COMPRESSED):
+ *     GEVWS_INF_PENDING; it stops the chain, as above.
+ * Messages without END are PENDING as above.
+ *
+ * Malformed input makes the call GEVWS_ERR_INVALID on the device, as a record
+ * with conn >= n_conns does in gevws_inflate_ctx_async: a message record with
+ * conn >= n_conns (counted a record), and an OPEN input record of a connection
+ * that has a message in the batch with off % 16 != 0 or off + length >
+ * carry_src_bytes (counted a connection).  d_summary gets the status and the
+ * count in `errors`; nothing else is written, no slot is touched, and no
+ * address is formed from such a field.  GEVWS_ERR_CAPACITY is as above: nothing
+ * is written, the slots are untouched byte for byte, and the retry uses the
+ * same inputs.  d_carry_src starts on a 16-byte boundary and is read as whole
+ * vectors inside a record's [off, off + length) rounded down to 16, its last
+ * ragged bytes one by one; with a carry max_messages is at most 0x7FF00000. */
+#define GEVWS_CARRY_COMPRESSED 4u        /* gevws_carry.flags, beside OPEN: the bytes are compressed payload */
+#define GEVWS_CARRY_KEEP_COMPRESSED 1u   /* carry_flags */
+int gevws_join_carry_ext_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_frames, uint64_t max_frames,
+                               const gevws_message *d_messages, uint64_t max_messages, const int64_t *d_msg_of,
+                               const gevws_summary *d_msg_summary, const uint8_t *d_payload,
+                               const gevws_inflated *d_inflated /* may be NULL */,
+                               const gevws_summary *d_inflate_summary /* may be NULL */, uint32_t flags,
+                               gevws_body *d_bodies, uint8_t *d_out, uint64_t out_cap, gevws_summary *d_summary,
+                               const gevws_conn_msg *d_conn_msg, uint32_t n_conns,
+                               uint64_t max_message_bytes /* 1 .. 2^32-1 */,
+                               const gevws_carry *d_carry_in /* may be NULL: every connection fresh */,
+                               const uint8_t *d_carry_src, uint64_t carry_src_bytes,
+                               gevws_carry *d_carry_out, uint8_t *d_carry_dst, uint64_t carry_cap,
+                               gevws_summary *d_carry_summary, uint32_t carry_flags);
+int gevws_inflate_carry_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_frames, uint64_t max_frames,
+                              const gevws_message *d_messages, uint64_t max_messages, const int64_t *d_msg_of,
+                              const gevws_summary *d_msg_summary, const uint8_t *d_payload,
+                              uint64_t max_message_bytes, gevws_msg_state *d_state /* may be NULL */,
+                              gevws_inflated *d_inflated, uint8_t *d_out, uint64_t out_cap, gevws_summary *d_summary,
+                              const uint8_t *d_conn_ext, uint8_t *d_inf_ctx, uint32_t n_conns,
+                              const gevws_carry *d_carry_in, const uint8_t *d_carry_src, uint64_t carry_src_bytes);
 
 /* gevws_reply_bodies_async is the message-level stand-in for the user's
  * handler, as gevws_dispatch_async's policy is at frame level: with

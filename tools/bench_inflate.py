@@ -22,6 +22,18 @@ both (alternating in one process), and zlib with a persistent decompressobj
 per connection.  Two JSON lines with "mode": "takeover".
 
     python tools/bench_inflate.py --takeover [--commit ID]
+
+--carry measures compressed messages that span two passes
+(gevws_inflate_carry_async, gevws_join_carry_ext_async) on the same shapes,
+with or without --takeover: every connection's stream is cut in two inside its
+middle message (the only one, without --takeover), at the middle of that
+message's payload.  Pass 1 holds the messages before it and its first half as
+an open fragment, pass 2 its second half with the FIN and the messages behind
+it.  One JSON line per case with "mode": "carry": the END pass's inflate beside
+the plain call over the same messages whole in one batch (alternating), the
+open pass's inflate and join, and the bytes the join moved into the carry.
+
+    python tools/bench_inflate.py --carry [--takeover] [--commit ID]
 """
 from __future__ import annotations
 
@@ -68,10 +80,10 @@ def deflate(data: bytes, level: int) -> bytes:
     return s[:-4]
 
 
-def wire_frame(payload: bytes, key: bytes):
+def wire_frame(payload: bytes, key: bytes, b0: int = 0xC1):
     import numpy as np
     L = len(payload)
-    hdr = bytes([0xC1]) + (bytes([0x80 | L]) if L <= 125 else bytes([0x80 | 126]) + L.to_bytes(2, "big") if L <= 0xFFFF
+    hdr = bytes([b0]) + (bytes([0x80 | L]) if L <= 125 else bytes([0x80 | 126]) + L.to_bytes(2, "big") if L <= 0xFFFF
                            else bytes([0x80 | 127]) + L.to_bytes(8, "big")) + key  # FIN | RSV1 | text, masked
     body = np.frombuffer(payload, np.uint8) ^ np.resize(np.frombuffer(key, np.uint8), L)
     return np.concatenate([np.frombuffer(hdr, np.uint8), body])
@@ -247,6 +259,166 @@ def takeover_main(args):
     eng.close()
 
 
+def carry_main(args):
+    """--carry: see the module docstring."""
+    import numpy as np
+    import torch
+
+    import gev_amd
+
+    rng = np.random.default_rng(0x636172)
+    cases = []  # (name, connections, ext byte, per-connection scripts of (text, payload))
+    if args.takeover:
+        scripts = []
+        for _ in range(TAKEOVER_SCRIPTS):
+            c = zlib.compressobj(6, zlib.DEFLATED, -15)
+            ts = [text(TAKEOVER_BYTES - 32 + int(rng.integers(0, 64)), rng) for _ in range(TAKEOVER_MSGS)]
+            scripts.append([(t, (c.compress(t) + c.flush(zlib.Z_SYNC_FLUSH))[:-4]) for t in ts])
+        cases.append(("takeover", TAKEOVER_CONNS, 3, scripts))
+    else:
+        for shape in args.shapes.split(","):
+            n, size = SHAPES[shape]
+            texts = [text(size, rng) for _ in range(DISTINCT)]
+            for kind in args.kinds.split(","):
+                cases.append((f"{shape}/{kind}", n, 1, [[(t, deflate(t, LEVELS[kind]))] for t in texts]))
+    dev = torch.device("cuda", 0)
+    eng = gev_amd.Engine(0)
+
+    def key():
+        return bytes(rng.integers(1, 256, 4).astype("u1"))
+
+    for name, n, ext_byte, scripts in cases:
+        per, ns = len(scripts[0]), len(scripts)
+        mid = per // 2
+        nm = n * per
+        limit = max(len(t) for sc in scripts for t, _ in sc)
+        inflated_bytes = sum(len(t) for i in range(n) for t, _ in scripts[i % ns])
+
+        def batch(streams, max_frames):
+            lens = np.array([streams[i % ns].size for i in range(n)], np.int64)
+            offs = np.concatenate([[0], np.cumsum(lens)[:-1]])
+            in_bytes = int(lens.sum())
+            arena = torch.zeros(in_bytes + gev_amd.IN_PAD, dtype=torch.uint8, device=dev)
+            arena[:in_bytes] = torch.from_numpy(np.concatenate([streams[i % ns] for i in range(n)])).to(dev)
+            cap = in_bytes + 16 * max_frames
+            return dict(arena=arena, in_bytes=in_bytes, conns=torch.from_numpy(np.stack([offs, lens], 1)).to(dev),
+                        cap=cap, out=eng.alloc_batch(n, max_frames, cap), frames=max_frames)
+
+        whole = batch([np.concatenate([wire_frame(p, key()) for _, p in sc]) for sc in scripts], nm)
+        first, second = [], []
+        for sc in scripts:
+            p = sc[mid][1]
+            h = len(p) // 2
+            first.append(np.concatenate([wire_frame(q, key()) for _, q in sc[:mid]] + [wire_frame(p[:h], key(), 0x41)]))
+            second.append(np.concatenate([wire_frame(p[h:], key(), 0x80)] + [wire_frame(q, key()) for _, q in sc[mid + 1:]]))
+        p1, p2 = batch(first, n * (mid + 1)), batch(second, n * (per - mid))
+        carried = sum(len(scripts[i % ns][mid][1]) // 2 for i in range(n))
+        carry_cap = sum((len(scripts[i % ns][mid][1]) // 2 + 15) // 16 * 16 for i in range(n))
+        ext = torch.full((n,), ext_byte, dtype=torch.uint8, device=dev)
+        ctx = torch.zeros((n, gev_amd.INF_CTX_BYTES), dtype=torch.uint8, device=dev) if args.takeover else None
+        state = torch.zeros((n, 8), dtype=torch.uint8, device=dev)
+        msgs = torch.empty((nm, 32), dtype=torch.uint8, device=dev)
+        msg_of = torch.empty(nm, dtype=torch.int64, device=dev)
+        conn_msg = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+        msum, isum, jsum, csum = (torch.zeros(64, dtype=torch.uint8, device=dev) for _ in range(4))
+        inflated = torch.empty((nm, 32), dtype=torch.uint8, device=dev)
+        bodies = torch.empty((nm, 32), dtype=torch.uint8, device=dev)
+        out_cap = nm * ((limit + 15) // 16 * 16)
+        d_out = torch.empty(out_cap + gev_amd.IN_PAD, dtype=torch.uint8, device=dev)
+        crec = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+        czero = torch.zeros((n, 32), dtype=torch.uint8, device=dev)  # the carry in front of the first pass
+        cdst = torch.zeros(carry_cap + gev_amd.IN_PAD, dtype=torch.uint8, device=dev)
+        t = {k: [] for k in ("whole", "open_inflate", "open_join", "end_inflate")}
+
+        def front(b):
+            eng.decode_async(b["arena"], b["in_bytes"], b["conns"], n, b["out"], b["frames"], b["cap"])
+            eng.messages_ext_async(b["out"].frames, b["frames"], b["out"].conn_out, n, b["out"].summary,
+                                   b["out"].payload, state, msgs, b["frames"], msg_of, conn_msg, msum, ext)
+
+        def inflate(b, carry):
+            o = b["out"]
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            e[0].record()
+            if carry is None:  # the call before the carry
+                eng.inflate_ctx_async(o.frames, b["frames"], msgs, b["frames"], msg_of, msum, o.payload, limit, state,
+                                      inflated, d_out, out_cap, isum, ext if ctx is not None else None, ctx, n)
+            else:
+                eng.inflate_carry_async(o.frames, b["frames"], msgs, b["frames"], msg_of, msum, o.payload, limit,
+                                        state, inflated, d_out, out_cap, isum, ext if ctx is not None else None, ctx,
+                                        n, carry[0], carry[1], carry[2])
+            e[1].record()
+            return e
+
+        def check(want_frames, want_len):
+            s = isum.cpu().numpy().view(gev_amd.SUMMARY_DTYPE)[0]
+            assert (int(s["status"]), int(s["frames"]), int(s["errors"]), int(s["payload_len"])) == \
+                (0, want_frames, 0, want_len), (name, s)
+
+        def one_round(timed):
+            state.zero_()
+            if ctx is not None:
+                ctx.zero_()
+            front(whole)
+            ew = inflate(whole, None)
+            torch.cuda.synchronize()
+            if not timed:
+                check(nm, inflated_bytes)
+            state.zero_()
+            if ctx is not None:
+                ctx.zero_()
+            front(p1)
+            e1 = inflate(p1, (czero, cdst, 0))
+            ej = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ej[0].record()
+            eng.join_carry_ext_async(p1["out"].frames, p1["frames"], msgs, p1["frames"], msg_of, msum,
+                                     p1["out"].payload, inflated, isum, gev_amd.JOIN_ALL, bodies, d_out, out_cap, jsum,
+                                     conn_msg, n, 0xFFFFFFFF, None, None, 0, crec, cdst, carry_cap, csum,
+                                     gev_amd.CARRY_KEEP_COMPRESSED)
+            ej[1].record()
+            torch.cuda.synchronize()
+            if not timed:
+                c = csum.cpu().numpy().view(gev_amd.SUMMARY_DTYPE)[0]
+                assert (int(c["status"]), int(c["frames"]), int(c["payload_len"]), int(c["payload_bytes"])) == \
+                    (0, n, carried, carry_cap), (name, c)
+            front(p2)
+            e2 = inflate(p2, (crec, cdst, carry_cap))
+            torch.cuda.synchronize()
+            if not timed:
+                check(n * (per - mid), sum(len(x) for i in range(n) for x, _ in scripts[i % ns][mid:]))
+                rec = inflated.cpu().numpy().reshape(-1).view(gev_amd.INFLATED_DTYPE)
+                for i in (0, 1, n - 1):  # the carried message's bytes are its text
+                    want = scripts[i % ns][mid][0]
+                    o = int(rec["out_off"][i * (per - mid)])
+                    assert d_out[o:o + len(want)].cpu().numpy().tobytes() == want, (name, i)
+            else:
+                t["whole"].append(ew[0].elapsed_time(ew[1]))
+                t["open_inflate"].append(e1[0].elapsed_time(e1[1]))
+                t["open_join"].append(ej[0].elapsed_time(ej[1]))
+                t["end_inflate"].append(e2[0].elapsed_time(e2[1]))
+
+        for _ in range(args.warmup):
+            one_round(False)
+        for _ in range(args.rounds):
+            one_round(True)
+        line = {"path": "compressed messages cut in two passes inside the middle message: the END pass's "
+                        "gevws_inflate_carry_async beside the call without a carry over the same messages whole in "
+                        "one batch; the open pass's inflate and gevws_join_carry_ext_async",
+                "mode": "carry", "case": name, "takeover": bool(args.takeover), "commit": args.commit,
+                "connections": n, "messages_per_connection": per, "messages_in_end_pass": n * (per - mid),
+                "inflated_bytes": inflated_bytes, "carried_bytes": carried, "carry_arena_bytes": carry_cap,
+                "whole_inflate_ms": round(median(t["whole"]), 4),
+                "end_inflate_carry_ms": round(median(t["end_inflate"]), 4),
+                "open_inflate_carry_ms": round(median(t["open_inflate"]), 4),
+                "open_join_carry_ms": round(median(t["open_join"]), 4),
+                "open_join_read_plus_write_bytes": carried + carry_cap,
+                "rounds_ms": {k: [round(x, 4) for x in v] for k, v in t.items()},
+                "rounds": args.rounds, "warmup": args.warmup}
+        print(json.dumps(line), flush=True)
+        del whole, p1, p2, msgs, msg_of, inflated, bodies, d_out, cdst
+        torch.cuda.empty_cache()
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -256,8 +428,12 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the zlib baselines")
     ap.add_argument("--takeover", action="store_true",
                     help="client context takeover against independently compressed messages (16 384 x 8 x ~512 B)")
-    ap.add_argument("--commit", default="", help="recorded in the --takeover lines")
+    ap.add_argument("--carry", action="store_true",
+                    help="compressed messages that span two passes; with --takeover on the takeover shape")
+    ap.add_argument("--commit", default="", help="recorded in the --takeover and --carry lines")
     args = ap.parse_args()
+    if args.carry:
+        return carry_main(args)
     if args.takeover:
         return takeover_main(args)
     import numpy as np
