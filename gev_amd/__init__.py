@@ -32,6 +32,8 @@ from ._abi import DEF_CTX_BYTES, EXT_SERVER_TAKEOVER, NEGOTIATE_SERVER_TAKEOVER
 from ._abi import BODY_INFLATED, BODY_JOINED, BODY_WHOLE, JOIN_ALL
 from ._abi import CARRY_COMPRESSED, CARRY_KEEP_COMPRESSED, CARRY_LOST, CARRY_OPEN
 from ._abi import HANDLER_ECHO_BINARY, HANDLER_ECHO_TEXT, HANDLER_NONE
+from ._abi import (CONTROL_NO_PING_FOR_PONG, CTL_FAILED, CTL_SHUTDOWN, MSG_ERR_CLOSED, WIRE_CONTROL, WIRE_DEFLATED,
+                   WIRE_PLAIN)
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
                    SUMMARY_UNORDERED, TILE, Header)
@@ -67,6 +69,11 @@ assert FRAME_DTYPE.itemsize == 32 and CONN_OUT_DTYPE.itemsize == 32 and INFLATED
 CARRY_DTYPE = np.dtype([("off", "<u8"), ("length", "<u8"), ("opcode", "u1"), ("flags", "u1"), ("status", "u1"),
                         ("reserved", "u1", (13,))])
 assert BODY_DTYPE.itemsize == 32 and CARRY_DTYPE.itemsize == 32
+CONN_CTL_DTYPE = np.dtype([("cut_frame", "<u8"), ("close_code", "<u4"), ("flags", "<u4"), ("reserved", "<u8", (2,))])
+SEND_DTYPE = np.dtype([("off", "<u8"), ("len", "<u8"), ("frame", "<u8"), ("conn", "<u4"), ("wire", "<u4")])
+CONN_SEND_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("bytes", "<u8"), ("flags", "<u4"),
+                            ("reserved", "<u4")])
+assert CONN_CTL_DTYPE.itemsize == 32 and SEND_DTYPE.itemsize == 32 and CONN_SEND_DTYPE.itemsize == 32
 assert DEFLATE_MSG_DTYPE.itemsize == 24 and OUT_FRAME_DTYPE.itemsize == 32
 assert MSG_STATE_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 32 and CONN_MSG_DTYPE.itemsize == 32
 assert SUMMARY_DTYPE.itemsize == 64 and SYNTH_DTYPE.itemsize == 24
@@ -397,6 +404,43 @@ class Echo:
     plain_off: np.ndarray
     reply_of: np.ndarray
     deflated: Optional["Deflated"] = None   # the deflate step's records and payloads
+
+
+@dataclass
+class Responses:
+    """What Engine.respond sends: the three wire buffers (the Echo's two and
+    the control replies'), the control step's tables (numpy) and the send plan
+    (device tensors): send[k] says which bytes of which wire go out k-th,
+    conn_send[c] which entries are connection c's."""
+    echo: "Echo"
+    ctl_wire: "object"        # uint8: the control replies' wire bytes
+    ctl_conn: np.ndarray      # uint32 [replies]
+    ctl_of: np.ndarray        # int64 [frames]: frame -> control reply or -1
+    msg_end: np.ndarray       # uint64 [messages]: the message's last data frame, or 2^64 - 1
+    conn_ctl: np.ndarray      # CONN_CTL_DTYPE [n_conns]
+    ctl_summary: np.ndarray   # SUMMARY_DTYPE: the control step's
+    send: "object"            # uint8 [max_sends, 32] (gevws_send records)
+    conn_send: "object"       # uint8 [n_conns, 32]   (gevws_conn_send)
+    summary: "object"         # uint8 [64]            (the plan's gevws_summary)
+    n_conns: int
+
+    def summary_host(self) -> np.ndarray:
+        return self.summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
+
+    def send_host(self) -> np.ndarray:
+        n = int(self.summary_host()["frames"])
+        return self.send[:n].cpu().numpy().reshape(-1).view(SEND_DTYPE)
+
+    def conn_send_host(self) -> np.ndarray:
+        return self.conn_send[: self.n_conns].cpu().numpy().reshape(-1).view(CONN_SEND_DTYPE)
+
+    def conn_bytes(self, c: int) -> bytes:
+        """The bytes to write to connection c's socket: its plan entries' segments in order."""
+        wires = [w.cpu().numpy() for w in (self.echo.plain_wire, self.echo.def_wire, self.ctl_wire)]
+        cs, send = self.conn_send_host()[c], self.send_host()
+        first, count = int(cs["first"]), int(cs["count"])
+        return b"".join(wires[int(e["wire"])][int(e["off"]): int(e["off"]) + int(e["len"])].tobytes()
+                        for e in send[first: first + count])
 
 
 class _DevAddr:
@@ -1063,6 +1107,13 @@ class Engine:
         (or None), contexts: uint8 [n_conns, DEF_CTX_BYTES] for connections with
         EXT_SERVER_TAKEOVER, flags: the deflate step's.  The bodies come from a
         join with JOIN_ALL."""
+        return self._echo_chain(out, msgs, bodies, policy, conn_ext, window_bits, contexts, flags, stream)[0]
+
+    def _echo_chain(self, out: "Batch", msgs: "Messages", bodies: "Bodies", policy: int, conn_ext, window_bits,
+                    contexts, flags: int, stream):
+        """echo_messages' chain; beside the Echo, what the send plan reads of it
+        on the device: (reply_of, [(offset table, encode summary) of the deflated
+        wire, of the plain wire])."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n, n_conns = bodies.n_messages, out.n_conns
@@ -1074,7 +1125,7 @@ class Engine:
         empty = Echo(z(0), np.zeros(0, np.uint32), np.zeros(0, np.uint64), z(0), np.zeros(0, np.uint32),
                      np.zeros(0, np.uint64), np.zeros(0, np.int64))
         if n == 0:
-            return empty
+            return empty, reply_of, [(torch.zeros(1, dtype=torch.int64, device=dev), z(64)) for _ in range(2)]
         self.reply_bodies_async(bodies.bodies, n, msgs.summary, bodies.summary, policy, conn_ext, window_bits, n_conns,
                                 def_msgs, def_conn, def_sum, plain, plain_conn, plain_sum, reply_of, stream)
         torch.cuda.synchronize(self.device)
@@ -1099,7 +1150,7 @@ class Engine:
         s = res.summary_host()
         if int(s["status"]) != OK:
             raise RuntimeError(f"echo_messages: deflate: {status_string(int(s['status']))}")
-        wires = []
+        wires, tables = [], []
         for recs, gate, payload, total in (
                 (res.frames, res.summary, res.out, int(s["payload_len"])),
                 (plain, plain_sum, bodies.out,
@@ -1115,9 +1166,96 @@ class Engine:
             if int(es["status"]) != OK:
                 raise RuntimeError(f"echo_messages: encode: {status_string(int(es['status']))}")
             wires.append((wire[: int(es["payload_bytes"])], off[:k].cpu().numpy().astype(np.uint64)))
+            tables.append((off, esum))
         return Echo(def_wire=wires[0][0], def_conn=def_conn[:nd].cpu().numpy().view(np.uint32), def_off=wires[0][1],
                     plain_wire=wires[1][0], plain_conn=plain_conn[:npl].cpu().numpy().view(np.uint32),
-                    plain_off=wires[1][1], reply_of=reply_of[:n].cpu().numpy(), deflated=res)
+                    plain_off=wires[1][1], reply_of=reply_of[:n].cpu().numpy(), deflated=res), reply_of, tables
+
+    def control_async(self, frames, max_frames: int, conn_out, n_conns: int, decoded, payload, aux_off: int,
+                      aux_cap: int, msg_of, messages, max_messages: int, conn_msg, msg_summary, bodies, join_summary,
+                      flags: int, ctl, ctl_conn, ctl_of, msg_end, conn_ctl, summary, stream=None) -> None:
+        """gevws_control_async on device tensors: the control replies and the
+        failure closes up to each connection's cut, the bodies behind it
+        stripped in place."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        st = lib.gevws_control_async(
+            self._ctx, _stream_handle(stream), frames.data_ptr(), max_frames, conn_out.data_ptr(), n_conns,
+            decoded.data_ptr(), payload.data_ptr(), aux_off, aux_cap, msg_of.data_ptr(), ptr(messages), max_messages,
+            conn_msg.data_ptr(), msg_summary.data_ptr(), ptr(bodies), join_summary.data_ptr(), flags, ctl.data_ptr(),
+            ctl_conn.data_ptr(), ctl_of.data_ptr(), ptr(msg_end), conn_ctl.data_ptr(), summary.data_ptr())
+        if st != OK:
+            raise RuntimeError(f"gevws_control_async: {status_string(st)}")
+
+    def send_plan_async(self, max_frames: int, decoded, conn_out, n_conns: int, msg_of, msg_end, reply_of,
+                        max_messages: int, msg_summary, join_summary, conn_ext, ctl_of, conn_ctl, ctl_summary,
+                        plain_off, plain_encoded, def_off, def_encoded, ctl_off, ctl_encoded, send, max_sends: int,
+                        conn_send, summary, stream=None) -> None:
+        """gevws_send_plan_async on device tensors: which bytes of the three
+        wire buffers go to which connection, in send order."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        st = lib.gevws_send_plan_async(
+            self._ctx, _stream_handle(stream), max_frames, decoded.data_ptr(), conn_out.data_ptr(), n_conns,
+            msg_of.data_ptr(), ptr(msg_end), ptr(reply_of), max_messages, msg_summary.data_ptr(),
+            join_summary.data_ptr(), ptr(conn_ext), ctl_of.data_ptr(), conn_ctl.data_ptr(), ctl_summary.data_ptr(),
+            plain_off.data_ptr(), plain_encoded.data_ptr(), def_off.data_ptr(), def_encoded.data_ptr(),
+            ctl_off.data_ptr(), ctl_encoded.data_ptr(), ptr(send), max_sends, conn_send.data_ptr(),
+            summary.data_ptr())
+        if st != OK:
+            raise RuntimeError(f"gevws_send_plan_async: {status_string(st)}")
+
+    def respond(self, out: "Batch", msgs: "Messages", bodies: "Bodies", policy: int, conn_ext, window_bits=None,
+                contexts=None, flags: int = 0, control_flags: int = 0, stream=None) -> "Responses":
+        """Everything a pass sends: control -> reply -> deflate (with contexts:
+        deflate_ctx) -> the three encodes -> plan.  The arguments are
+        echo_messages'; control_flags: the control step's.  `bodies` (from a join
+        with JOIN_ALL) is rewritten in place: messages behind a connection's cut
+        are no longer delivered.  The close bodies go into the aux slots
+        alloc_batch reserved, one per connection at the most."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        n_conns, nf, nm = out.n_conns, msgs.n_frames, bodies.n_messages
+        if out.aux_slots < n_conns:
+            raise ValueError(f"respond: the batch reserves {out.aux_slots} aux slots for {n_conns} connections")
+        aux_cap = _abi.AUX_SLOT * out.aux_slots
+        aux_off = (out.payload.numel() - 16 - aux_cap) // 16 * 16
+        z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        capf, capm, capc = max(nf, 1), max(nm, 1), max(n_conns, 1)
+        ctl, ctl_conn, ctl_sum = z(capf, 32), z(capf, dt=torch.int32), z(64)
+        ctl_of = torch.full((capf,), -1, dtype=torch.int64, device=dev)
+        msg_end = torch.full((capm,), -1, dtype=torch.int64, device=dev)
+        conn_ctl = z(capc, 32)
+        conn_ctl.view(torch.int64)[:, 0] = -1  # no cut
+        self.control_async(out.frames, nf, out.conn_out, n_conns, out.summary, out.payload, aux_off, aux_cap,
+                           msgs.msg_of, msgs.messages, nm, msgs.conn_msg, msgs.summary, bodies.bodies, bodies.summary,
+                           control_flags, ctl, ctl_conn, ctl_of, msg_end, conn_ctl, ctl_sum, stream)
+        torch.cuda.synchronize(self.device)
+        cs = ctl_sum.cpu().numpy().view(SUMMARY_DTYPE)[0]
+        if int(cs["status"]) != OK:
+            raise RuntimeError(f"respond: control: {status_string(int(cs['status']))} ({int(cs['errors'])})")
+        echo, reply_of, tables = self._echo_chain(out, msgs, bodies, policy, conn_ext, window_bits, contexts, flags,
+                                                  stream)
+        nr = int(cs["frames"])
+        total = int(ctl[:nr].cpu().numpy().reshape(-1).view(OUT_FRAME_DTYPE)["payload_len"].sum())
+        wcap = total + 14 * nr + 16
+        ctl_wire = torch.empty(wcap + _abi.OUT_PAD, dtype=torch.uint8, device=dev)
+        ctl_off, ctl_enc = torch.zeros(capf, dtype=torch.int64, device=dev), z(64)
+        self.encode_replies_async(ctl, nf, ctl_sum, out.payload, ctl_wire, wcap, ctl_off, ctl_enc, stream)
+        send, conn_send, plan_sum = z(capf, 32), z(capc, 32), z(64)
+        (def_off, def_enc), (plain_off, plain_enc) = tables
+        self.send_plan_async(nf, out.summary, out.conn_out, n_conns, msgs.msg_of, msg_end, reply_of, nm, msgs.summary,
+                             bodies.summary, conn_ext, ctl_of, conn_ctl, ctl_sum, plain_off, plain_enc, def_off,
+                             def_enc, ctl_off, ctl_enc, send, nf, conn_send, plan_sum, stream)
+        torch.cuda.synchronize(self.device)
+        es = ctl_enc.cpu().numpy().view(SUMMARY_DTYPE)[0]
+        ps = plan_sum.cpu().numpy().view(SUMMARY_DTYPE)[0]
+        if int(es["status"]) != OK or int(ps["status"]) != OK:
+            raise RuntimeError(f"respond: encode {status_string(int(es['status']))}, plan "
+                               f"{status_string(int(ps['status']))} ({int(ps['errors'])})")
+        return Responses(echo=echo, ctl_wire=ctl_wire[: int(es["payload_bytes"])],
+                         ctl_conn=ctl_conn[:nr].cpu().numpy().view(np.uint32), ctl_of=ctl_of[:nf].cpu().numpy(),
+                         msg_end=msg_end[:nm].cpu().numpy().view(np.uint64),
+                         conn_ctl=conn_ctl[:n_conns].cpu().numpy().reshape(-1).view(CONN_CTL_DTYPE), ctl_summary=cs,
+                         send=send, conn_send=conn_send, summary=plan_sum, n_conns=n_conns)
 
     def messages(self, out: "Batch", state=None, max_messages: Optional[int] = None, stream=None, *,
                  conn_ext=None) -> "Messages":

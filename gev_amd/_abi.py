@@ -88,6 +88,12 @@ CARRY_OPEN = 1
 CARRY_LOST = 2
 CARRY_COMPRESSED = 4  # beside CARRY_OPEN: the bytes are compressed payload (gevws_join_carry_ext_async)
 CARRY_KEEP_COMPRESSED = 1  # gevws_join_carry_ext_async carry_flags bit
+# the control step and the send plan (gevws_control_async, gevws_send_plan_async)
+MSG_ERR_CLOSED = 9  # gevws_body.status of a message behind its connection's cut
+CONTROL_NO_PING_FOR_PONG = 1  # gevws_control_async flag
+CTL_SHUTDOWN = 1  # gevws_conn_ctl.flags: the connection has a cut
+CTL_FAILED = 2  # beside it: the cut is a failure, close_code was sent
+WIRE_PLAIN, WIRE_DEFLATED, WIRE_CONTROL = 0, 1, 2  # gevws_send.wire
 
 IN_PAD = 64
 MEM_DEFAULT, MEM_FINE, MEM_UNCACHED = 0, 1, 2  # gevws_device_alloc kinds
@@ -198,6 +204,24 @@ class Carry(ctypes.Structure):
                 ("flags", ctypes.c_uint8), ("status", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 13)]
 
 
+class ConnCtl(ctypes.Structure):
+    """gevws_conn_ctl: one connection's cut (gevws_control_async)."""
+    _fields_ = [("cut_frame", ctypes.c_uint64), ("close_code", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint64 * 2)]
+
+
+class Send(ctypes.Structure):
+    """gevws_send: one reply's bytes in its wire buffer (gevws_send_plan_async)."""
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("frame", ctypes.c_uint64),
+                ("conn", ctypes.c_uint32), ("wire", ctypes.c_uint32)]
+
+
+class ConnSend(ctypes.Structure):
+    """gevws_conn_send: one connection's entries of the send plan."""
+    _fields_ = [("first", ctypes.c_uint64), ("count", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class Reject(ctypes.Structure):
     """gevws_reject: RejectConnectionError options (ws/errors.go:81-129)."""
     _fields_ = [("code", ctypes.c_int32), ("plain", ctypes.c_int32), ("reason", ctypes.c_void_p),
@@ -244,6 +268,7 @@ assert ctypes.sizeof(ConnIn) == 16 and ctypes.sizeof(ConnOut) == 32
 assert ctypes.sizeof(Summary) == 64 and ctypes.sizeof(SynthDesc) == 24
 assert ctypes.sizeof(MsgState) == 8 and ctypes.sizeof(Message) == 32 and ctypes.sizeof(ConnMsg) == 32
 assert ctypes.sizeof(Inflated) == 32 and ctypes.sizeof(Body) == 32 and ctypes.sizeof(Carry) == 32
+assert ctypes.sizeof(ConnCtl) == 32 and ctypes.sizeof(Send) == 32 and ctypes.sizeof(ConnSend) == 32
 
 P = ctypes.c_void_p
 U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -331,6 +356,11 @@ SIGNATURES = {
                                                  P, P, ctypes.c_uint64]),
     "gevws_reply_bodies_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, ctypes.c_int, P, P, ctypes.c_uint32,
                                                 P, P, P, P, P, P, P]),
+    "gevws_control_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint32, P, P, ctypes.c_uint64,
+                                           ctypes.c_uint64, P, P, ctypes.c_uint64, P, P, P, P, ctypes.c_uint32, P, P,
+                                           P, P, P, P]),
+    "gevws_send_plan_async": (ctypes.c_int, [P, P, ctypes.c_uint64, P, P, ctypes.c_uint32, P, P, P, ctypes.c_uint64,
+                                             P, P, P, P, P, P, P, P, P, P, P, P, P, ctypes.c_uint64, P, P]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),
     "gevws_synth_async": (ctypes.c_int, [P, P, P, P, ctypes.c_uint64, ctypes.c_uint64]),
     "gevws_synth_verify_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P,

@@ -189,24 +189,6 @@ __device__ __forceinline__ uint64_t join_count(uint64_t max_messages, const gevw
   return gated_count(max_messages, msg_sum);
 }
 
-// The workgroup's partial {vals[0], .. vals[NV - 1], 0 ..} -> blk[row] (rows of NF fields).
-template <int NV, int NF = kBlkFields>
-__device__ __forceinline__ void block_partial(const uint64_t (&vals)[NV], uint64_t* __restrict__ blk, uint64_t row) {
-  __shared__ uint64_t s_part[NV][kWalkBlock / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const uint64_t sm = wave_sum(vals[k]);
-    if (lane == 0) s_part[k][wv] = sm;
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    uint64_t sm = 0;
-    for (int j = 0; j < kWalkBlock / 64; ++j) sm += s_part[threadIdx.x][j];
-    blk[row * NF + threadIdx.x] = sm;
-  }
-}
-
 // ------------------------------------------------------------------ 1. sizes
 template <bool CARRY>
 __global__ __launch_bounds__(kWalkBlock) void k_join_size(const gevws_message* __restrict__ msgs,

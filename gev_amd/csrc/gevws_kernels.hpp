@@ -293,6 +293,26 @@ __device__ __forceinline__ uint64_t gated_count(uint64_t n, const gevws_summary*
   return g.status != GEVWS_OK ? 0 : (g.frames < n ? g.frames : n);
 }
 
+// The workgroup's partial {vals[0], .. vals[NV - 1], 0 ..} -> blk[row] (rows of
+// NF fields; blockDim.x = kWalkBlock): what the count passes of the join, the
+// reply, the control step and the send plan hand to k_scan_blocks.
+template <int NV, int NF = kBlkFields>
+__device__ __forceinline__ void block_partial(const uint64_t (&vals)[NV], uint64_t* __restrict__ blk, uint64_t row) {
+  __shared__ uint64_t s_part[NV][kWalkBlock / 64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const uint64_t sm = wave_sum(vals[k]);
+    if (lane == 0) s_part[k][wv] = sm;
+  }
+  __syncthreads();
+  if (threadIdx.x < NV) {
+    uint64_t sm = 0;
+    for (int j = 0; j < kWalkBlock / 64; ++j) sm += s_part[threadIdx.x][j];
+    blk[row * NF + threadIdx.x] = sm;
+  }
+}
+
 // ------------------------------------------------------------------ 2. scan of block partials
 // SPLIT (decode): field 3 holds errors in its low 32 bits and the count of
 // out-of-order connections in its high 32 (k_walk_count) -> summary.errors and

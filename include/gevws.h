@@ -416,7 +416,7 @@ int gevws_handle_decoded_async(gevws_ctx *ctx, void *stream, const gevws_frame *
  * binary messages and of control frames are not validated (dispatch checks
  * the close reason).  A caller closes a failed connection with status 1002
  * (protocol error) for errors 1-5 and 1007 (invalid payload data) for 6
- * (section 7.4.1). */
+ * (section 7.4.1); gevws_control_async below builds that close frame. */
 enum {
     GEVWS_MSG_OK = 0,
     GEVWS_MSG_ERR_RSV = 1,
@@ -1219,6 +1219,165 @@ int gevws_reply_bodies_async(gevws_ctx *ctx, void *stream, const gevws_body *d_b
                              gevws_deflate_msg *d_def_msgs, uint32_t *d_def_conn, gevws_summary *d_def_summary,
                              gevws_out_frame *d_plain, uint32_t *d_plain_conn, gevws_summary *d_plain_summary,
                              int64_t *d_reply_of);
+
+/* The control step and the send plan: the message chain answers every frame
+ * a peer may send, closes a connection that failed a check, and states what
+ * is written to each socket and in which order.  Additions to ABI version 3:
+ * nothing above changes.  The chain of one pass is
+ *   decode -> messages -> inflate -> join -> control -> reply -> deflate ->
+ *   encode (plain list) -> encode (deflate records) -> encode (d_ctl) -> plan.
+ *
+ * gevws_control_async stands behind the join and before
+ * gevws_reply_bodies_async.  d_frames / max_frames / d_conn_out / n_conns /
+ * d_decoded / d_payload are the decode's, aux_off / aux_cap an aux region of
+ * d_payload as in gevws_dispatch_async (GEVWS_AUX_SLOT bytes a slot); d_msg_of /
+ * d_messages / max_messages / d_conn_msg / d_msg_summary the message pass's;
+ * d_bodies / d_join_summary the join's.  The frames are the first
+ * min(d_decoded->frames, max_frames), the messages the first
+ * min(d_msg_summary->frames, max_messages).
+ *
+ * The cut.  A connection's cut is its first frame, in stream order, that is
+ *   (a) a close frame (opcode 8);
+ *   (b) d_conn_msg[c].error_frame, when d_conn_msg[c].error is 1..6;
+ *   (c) the last data frame in this batch of the connection's first message
+ *       whose d_bodies record has status != GEVWS_MSG_OK (GEVWS_MSG_ERR_UTF8
+ *       found after inflating, GEVWS_MSG_ERR_DEFLATE, GEVWS_MSG_ERR_TOO_BIG).
+ * A frame that is both (a) and (b) -- a close frame that fails a frame check --
+ * counts as (b).  A connection that comes in failed (error != 0 with
+ * error_frame == UINT64_MAX), one with d_conn_out[c].status < 0 and one without
+ * frames have no cut and yield nothing: the host deals with them.
+ *
+ * Control replies: gevws_out_frame records in d_ctl over d_payload and its aux
+ * region (ready for gevws_encode_replies_async with d_summary as d_dispatched
+ * and the same d_payload), in frame order, from the frames up to and including
+ * the cut; every frame behind the cut is ignored.
+ *   - A ping gives a pong with the frame's payload in place.
+ *   - A pong gives a ping (util.go:54-56, as gevws_dispatch_async does) unless
+ *     GEVWS_CONTROL_NO_PING_FOR_PONG is set in `flags` (RFC 6455 section 5.5.3:
+ *     a pong needs no answer).
+ *   - A close frame -- the cut of kind (a) -- gives exactly the reply
+ *     gevws_dispatch_async gives (util.HandleClose; one code serves both).
+ *   - A cut of kind (b) or (c) gives the close of a failed connection: fin,
+ *     opcode 8, a 2-byte body in an aux slot (the code, no reason).  The code
+ *     is 1002 (protocol error) for errors 1-5, 1007 (invalid payload data) for
+ *     GEVWS_MSG_ERR_UTF8 and GEVWS_MSG_ERR_DEFLATE, 1009 (message too big) for
+ *     GEVWS_MSG_ERR_TOO_BIG, 1002 for any other status.  RFC 7692 names no code
+ *     for a stream that does not inflate; 1007 is this library's choice.
+ * Only the bytes of a body are written to its slot.
+ *
+ * Behind the cut.  Every message of the connection whose last data frame in
+ * this batch lies behind the cut loses its body: d_bodies[m] gets off = length
+ * = flags = 0 and status GEVWS_MSG_ERR_CLOSED (conn and opcode stay), so the
+ * reply step builds no reply for it and a takeover window sees only what is
+ * sent.  A message whose last data frame lies before the cut, or is the cut
+ * (the failed message itself, already undelivered), keeps its record.
+ *
+ * Tables.  d_ctl and d_ctl_conn hold max_frames entries: d_ctl_conn[k] is the
+ * connection of reply k.  d_ctl_of[f], for each of the frames, = the reply of
+ * frame f or -1 (gevws_dispatch_async's d_reply_of).  d_msg_end[m], for each of
+ * the messages, = the record index of its last data frame when it has
+ * GEVWS_MSG_END, else UINT64_MAX.  d_conn_ctl[c], for every connection:
+ * cut_frame (UINT64_MAX: none), close_code (0 unless GEVWS_CTL_FAILED) and
+ * flags -- GEVWS_CTL_SHUTDOWN for any cut (the reference's ShutdownWrite,
+ * wrap.go:52-56: the host sends what the plan lists and then stops feeding the
+ * connection), GEVWS_CTL_FAILED beside it for kinds (b) and (c).
+ *
+ * d_summary: frames = control replies, payload_bytes = aux slots used, errors
+ * = connections shut down.
+ *   - GEVWS_ERR_CAPACITY when the slots do not fit in aux_cap: the counts are
+ *     the need, and nothing but the summary is written -- d_bodies and every
+ *     table stay byte for byte, so the caller retries.
+ *   - A failed d_msg_summary or d_join_summary, no decoded frames or a failed
+ *     d_decoded, n_conns == 0 or max_frames == 0 give a zero summary; nothing
+ *     else is read or written.
+ *   - A d_msg_of entry outside the message table (not -1 and not below the
+ *     message count), or an error_frame (with error 1..6, not UINT64_MAX)
+ *     outside its connection's frames, makes the call GEVWS_ERR_INVALID on the
+ *     device: `errors` counts such connections, the other fields are zero and
+ *     nothing else is written.  The check runs before anything is indexed by
+ *     such a value.
+ *   - Any flag bit but GEVWS_CONTROL_NO_PING_FOR_PONG is GEVWS_ERR_INVALID from
+ *     the call; max_frames and max_messages are at most 2^32 - 1. */
+enum { GEVWS_MSG_ERR_CLOSED = 9 };   /* continues the GEVWS_MSG_* enum: gevws_body.status behind a cut */
+#define GEVWS_CONTROL_NO_PING_FOR_PONG 1u   /* call flag */
+#define GEVWS_CTL_SHUTDOWN 1u   /* gevws_conn_ctl.flags: the connection has a cut */
+#define GEVWS_CTL_FAILED   2u   /* beside it: the cut is a failure, close_code was sent */
+typedef struct gevws_conn_ctl {   /* 32 bytes per connection */
+    uint64_t cut_frame;     /* record index, or UINT64_MAX */
+    uint32_t close_code;    /* 1002 / 1007 / 1009 with GEVWS_CTL_FAILED, else 0 */
+    uint32_t flags;         /* GEVWS_CTL_* */
+    uint64_t reserved[2];
+} gevws_conn_ctl;
+int gevws_control_async(gevws_ctx *ctx, void *stream, const gevws_frame *d_frames, uint64_t max_frames,
+                        const gevws_conn_out *d_conn_out, uint32_t n_conns, const gevws_summary *d_decoded,
+                        uint8_t *d_payload, uint64_t aux_off, uint64_t aux_cap, const int64_t *d_msg_of,
+                        const gevws_message *d_messages, uint64_t max_messages, const gevws_conn_msg *d_conn_msg,
+                        const gevws_summary *d_msg_summary, gevws_body *d_bodies,
+                        const gevws_summary *d_join_summary, uint32_t flags, gevws_out_frame *d_ctl,
+                        uint32_t *d_ctl_conn, int64_t *d_ctl_of, uint64_t *d_msg_end, gevws_conn_ctl *d_conn_ctl,
+                        gevws_summary *d_summary);
+
+/* gevws_send_plan_async runs last, behind the three encodes
+ * (gevws_encode_replies_async of the reply step's plain list over the join's
+ * arena, of the deflate step's records over its d_out, and of d_ctl over the
+ * decode's payload arena).  Each wire comes with its d_out_off table and its
+ * encode summary: `frames` is the list's count, `payload_bytes` the wire total.
+ *
+ * A frame triggers at most one reply:
+ *   - its control reply, when d_ctl_of[f] >= 0 (wire 2);
+ *   - otherwise the reply to message m = d_msg_of[f], when d_msg_end[m] == f
+ *     and d_reply_of[m] >= 0: in the deflated wire (1) when the frame's
+ *     connection has GEVWS_EXT_DEFLATE in its d_conn_ext byte, else in the
+ *     plain wire (0; d_conn_ext == NULL: always).
+ * The frame's connection is the one whose d_conn_out range holds it.  Records
+ * are ordered by connection, then stream order, so the triggered replies in
+ * frame order are the send order: a pong stands before the reply to the
+ * message whose fragments surround the ping.
+ *
+ * d_send[k] (max_sends entries): reply k's bytes are wire[off, off + len) of
+ * wire `wire` -- off from that wire's table, len up to the next entry's offset
+ * or, for the list's last, the wire total -- triggered by `frame` of `conn`.
+ * d_conn_send[c], for every connection: its entries are d_send[first, first +
+ * count), `bytes` the sum of their len, `flags` d_conn_ctl[c].flags.
+ * d_summary: frames = entries, payload_bytes = the sum of len, errors =
+ * connections with GEVWS_CTL_SHUTDOWN.
+ *   - GEVWS_ERR_CAPACITY when there are more entries than max_sends: frames
+ *     holds the need and nothing else is written.
+ *   - A failed d_decoded, d_msg_summary, d_join_summary, d_ctl_summary or
+ *     encode summary, no decoded frames, n_conns == 0 or max_frames == 0 give
+ *     a zero summary; nothing else is read or written.
+ *   - A reply index outside its list's count, a d_msg_of entry outside the
+ *     message table, a triggering frame that belongs to no connection or a
+ *     table that decreases makes the call GEVWS_ERR_INVALID on the device:
+ *     `errors` counts such frames, the other fields are zero and nothing else
+ *     is written.  Every index is checked before it is used.
+ * d_msg_end and d_reply_of hold max_messages entries; the messages are the
+ * first min(d_msg_summary->frames, max_messages). */
+typedef struct gevws_send {        /* 32 bytes */
+    uint64_t off;      /* into its wire buffer */
+    uint64_t len;
+    uint64_t frame;    /* the decoded frame that triggered it */
+    uint32_t conn;
+    uint32_t wire;     /* 0 plain, 1 deflated, 2 control */
+} gevws_send;
+typedef struct gevws_conn_send {   /* 32 bytes per connection */
+    uint64_t first;    /* its entries: d_send[first, first + count) */
+    uint64_t count;
+    uint64_t bytes;    /* the sum of their len */
+    uint32_t flags;    /* GEVWS_CTL_*, copied from d_conn_ctl */
+    uint32_t reserved;
+} gevws_conn_send;
+int gevws_send_plan_async(gevws_ctx *ctx, void *stream, uint64_t max_frames, const gevws_summary *d_decoded,
+                          const gevws_conn_out *d_conn_out, uint32_t n_conns, const int64_t *d_msg_of,
+                          const uint64_t *d_msg_end, const int64_t *d_reply_of, uint64_t max_messages,
+                          const gevws_summary *d_msg_summary, const gevws_summary *d_join_summary,
+                          const uint8_t *d_conn_ext /* may be NULL */, const int64_t *d_ctl_of,
+                          const gevws_conn_ctl *d_conn_ctl, const gevws_summary *d_ctl_summary,
+                          const uint64_t *d_plain_off, const gevws_summary *d_plain_encoded,
+                          const uint64_t *d_def_off, const gevws_summary *d_def_encoded,
+                          const uint64_t *d_ctl_off, const gevws_summary *d_ctl_encoded,
+                          gevws_send *d_send, uint64_t max_sends, gevws_conn_send *d_conn_send,
+                          gevws_summary *d_summary);
 
 /* Measurement helper, not on the reference path: n bytes (n % 16 == 0, d_dst
  * 16-byte aligned, d_src any alignment) copied with the unmask kernel's
