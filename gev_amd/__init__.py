@@ -74,6 +74,8 @@ SEND_DTYPE = np.dtype([("off", "<u8"), ("len", "<u8"), ("frame", "<u8"), ("conn"
 CONN_SEND_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("bytes", "<u8"), ("flags", "<u4"),
                             ("reserved", "<u4")])
 assert CONN_CTL_DTYPE.itemsize == 32 and SEND_DTYPE.itemsize == 32 and CONN_SEND_DTYPE.itemsize == 32
+CONN_BUF_DTYPE = np.dtype([("off", "<u8"), ("bytes", "<u8"), ("flags", "<u4"), ("reserved", "<u4", (3,))])
+assert CONN_BUF_DTYPE.itemsize == 32
 assert DEFLATE_MSG_DTYPE.itemsize == 24 and OUT_FRAME_DTYPE.itemsize == 32
 assert MSG_STATE_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 32 and CONN_MSG_DTYPE.itemsize == 32
 assert SUMMARY_DTYPE.itemsize == 64 and SYNTH_DTYPE.itemsize == 24
@@ -423,9 +425,22 @@ class Responses:
     conn_send: "object"       # uint8 [n_conns, 32]   (gevws_conn_send)
     summary: "object"         # uint8 [64]            (the plan's gevws_summary)
     n_conns: int
+    # with respond(gather=True): every connection's bytes in one buffer (gevws_send_gather_async)
+    send_buf: Optional["object"] = None           # uint8, cut to the gather's payload_bytes
+    conn_buf: Optional[np.ndarray] = None         # CONN_BUF_DTYPE [n_conns]
+    gather_summary: Optional[np.ndarray] = None   # SUMMARY_DTYPE: the gather's
 
     def summary_host(self) -> np.ndarray:
         return self.summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
+
+    def host_sends(self) -> List[memoryview]:
+        """What the host writes to each socket: one device-to-host copy of the
+        send buffer, then connection c's span of it as element c (empty: nothing
+        to send).  Needs respond(gather=True)."""
+        if self.send_buf is None or self.conn_buf is None:
+            raise ValueError("host_sends: the pass was not gathered (respond(gather=True))")
+        host = memoryview(self.send_buf.cpu().numpy())
+        return [host[int(b["off"]): int(b["off"]) + int(b["bytes"])] for b in self.conn_buf]
 
     def send_host(self) -> np.ndarray:
         n = int(self.summary_host()["frames"])
@@ -1203,14 +1218,57 @@ class Engine:
         if st != OK:
             raise RuntimeError(f"gevws_send_plan_async: {status_string(st)}")
 
+    def send_gather_async(self, send, max_sends: int, conn_send, n_conns: int, plan_summary, wires, wire_bytes,
+                          buf, buf_cap: int, conn_buf, summary, flags: int = 0, stream=None) -> None:
+        """gevws_send_gather_async on device tensors: every connection's plan
+        entries copied back to back into its 16-aligned span of `buf` (device
+        memory or a PinnedArena address).  wires: the three wire buffers (plain,
+        deflated, control; None: an empty one), wire_bytes: the readable bytes
+        of each."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        bases = (ctypes.c_void_p * 3)(*[ptr(w) for w in wires])
+        nbytes = (ctypes.c_uint64 * 3)(*[int(x) for x in wire_bytes])
+        st = lib.gevws_send_gather_async(
+            self._ctx, _stream_handle(stream), ptr(send), max_sends, conn_send.data_ptr(), n_conns,
+            plan_summary.data_ptr(), ctypes.addressof(bases), ctypes.addressof(nbytes), flags, ptr(buf), buf_cap,
+            conn_buf.data_ptr(), summary.data_ptr())
+        if st != OK:
+            raise RuntimeError(f"gevws_send_gather_async: {status_string(st)}")
+
+    def _gather(self, send, max_sends: int, conn_send, n_conns: int, plan_sum, plan_bytes: int, wires, stream):
+        """respond's last step: the buffer sized from the plan's summary, grown
+        once on ERR_CAPACITY.  -> (send_buf, conn_buf, the gather's summary)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        cap = (plan_bytes + 16 * n_conns + 15) // 16 * 16
+        conn_buf = torch.zeros((max(n_conns, 1), 32), dtype=torch.uint8, device=dev)
+        gsum = torch.zeros(64, dtype=torch.uint8, device=dev)
+        for attempt in range(2):
+            buf = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+            self.send_gather_async(send, max_sends, conn_send, n_conns, plan_sum, wires,
+                                   [int(w.numel()) for w in wires], buf, cap, conn_buf, gsum, 0, stream)
+            torch.cuda.synchronize(self.device)
+            gs = gsum.cpu().numpy().view(SUMMARY_DTYPE)[0]
+            if int(gs["status"]) == ERR_CAPACITY and attempt == 0:
+                cap = int(gs["payload_bytes"])
+                continue
+            if int(gs["status"]) != OK:
+                raise RuntimeError(f"respond: gather: {status_string(int(gs['status']))} ({int(gs['errors'])})")
+            return (buf[: int(gs["payload_bytes"])],
+                    conn_buf[:n_conns].cpu().numpy().reshape(-1).view(CONN_BUF_DTYPE), gs)
+        raise RuntimeError("respond: gather: capacity retry failed")
+
     def respond(self, out: "Batch", msgs: "Messages", bodies: "Bodies", policy: int, conn_ext, window_bits=None,
-                contexts=None, flags: int = 0, control_flags: int = 0, stream=None) -> "Responses":
+                contexts=None, flags: int = 0, control_flags: int = 0, stream=None,
+                gather: bool = False) -> "Responses":
         """Everything a pass sends: control -> reply -> deflate (with contexts:
         deflate_ctx) -> the three encodes -> plan.  The arguments are
         echo_messages'; control_flags: the control step's.  `bodies` (from a join
         with JOIN_ALL) is rewritten in place: messages behind a connection's cut
         are no longer delivered.  The close bodies go into the aux slots
-        alloc_batch reserved, one per connection at the most."""
+        alloc_batch reserved, one per connection at the most.  gather=True ends
+        the chain with the gather: send_buf / conn_buf / gather_summary hold
+        every connection's bytes in one buffer (Responses.host_sends)."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n_conns, nf, nm = out.n_conns, msgs.n_frames, bodies.n_messages
@@ -1251,11 +1309,17 @@ class Engine:
         if int(es["status"]) != OK or int(ps["status"]) != OK:
             raise RuntimeError(f"respond: encode {status_string(int(es['status']))}, plan "
                                f"{status_string(int(ps['status']))} ({int(ps['errors'])})")
+        send_buf = conn_buf = gsum = None
+        if gather:
+            wires = (echo.plain_wire, echo.def_wire, ctl_wire[: int(es["payload_bytes"])])
+            send_buf, conn_buf, gsum = self._gather(send, nf, conn_send, n_conns, plan_sum, int(ps["payload_bytes"]),
+                                                    wires, stream)
         return Responses(echo=echo, ctl_wire=ctl_wire[: int(es["payload_bytes"])],
                          ctl_conn=ctl_conn[:nr].cpu().numpy().view(np.uint32), ctl_of=ctl_of[:nf].cpu().numpy(),
                          msg_end=msg_end[:nm].cpu().numpy().view(np.uint64),
                          conn_ctl=conn_ctl[:n_conns].cpu().numpy().reshape(-1).view(CONN_CTL_DTYPE), ctl_summary=cs,
-                         send=send, conn_send=conn_send, summary=plan_sum, n_conns=n_conns)
+                         send=send, conn_send=conn_send, summary=plan_sum, n_conns=n_conns, send_buf=send_buf,
+                         conn_buf=conn_buf, gather_summary=gsum)
 
     def messages(self, out: "Batch", state=None, max_messages: Optional[int] = None, stream=None, *,
                  conn_ext=None) -> "Messages":

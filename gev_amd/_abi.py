@@ -222,6 +222,12 @@ class ConnSend(ctypes.Structure):
                 ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class ConnBuf(ctypes.Structure):
+    """gevws_conn_buf: one connection's span of the send buffer (gevws_send_gather_async)."""
+    _fields_ = [("off", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 3)]
+
+
 class Reject(ctypes.Structure):
     """gevws_reject: RejectConnectionError options (ws/errors.go:81-129)."""
     _fields_ = [("code", ctypes.c_int32), ("plain", ctypes.c_int32), ("reason", ctypes.c_void_p),
@@ -269,6 +275,7 @@ assert ctypes.sizeof(Summary) == 64 and ctypes.sizeof(SynthDesc) == 24
 assert ctypes.sizeof(MsgState) == 8 and ctypes.sizeof(Message) == 32 and ctypes.sizeof(ConnMsg) == 32
 assert ctypes.sizeof(Inflated) == 32 and ctypes.sizeof(Body) == 32 and ctypes.sizeof(Carry) == 32
 assert ctypes.sizeof(ConnCtl) == 32 and ctypes.sizeof(Send) == 32 and ctypes.sizeof(ConnSend) == 32
+assert ctypes.sizeof(ConnBuf) == 32
 
 P = ctypes.c_void_p
 U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -361,6 +368,8 @@ SIGNATURES = {
                                            P, P, P, P]),
     "gevws_send_plan_async": (ctypes.c_int, [P, P, ctypes.c_uint64, P, P, ctypes.c_uint32, P, P, P, ctypes.c_uint64,
                                              P, P, P, P, P, P, P, P, P, P, P, P, P, ctypes.c_uint64, P, P]),
+    "gevws_send_gather_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint32, P, P, P, ctypes.c_uint32,
+                                               P, ctypes.c_uint64, P, P]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),
     "gevws_synth_async": (ctypes.c_int, [P, P, P, P, ctypes.c_uint64, ctypes.c_uint64]),
     "gevws_synth_verify_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P,

@@ -1379,6 +1379,64 @@ int gevws_send_plan_async(gevws_ctx *ctx, void *stream, uint64_t max_frames, con
                           gevws_send *d_send, uint64_t max_sends, gevws_conn_send *d_conn_send,
                           gevws_summary *d_summary);
 
+/* gevws_send_gather_async runs behind the plan: it puts every connection's
+ * reply bytes next to each other in one buffer, so the host sends a pass with
+ * one device-to-host copy (or none: d_buf may be mapped host memory) and one
+ * write(fd, buf + off, bytes) per connection.
+ *
+ * It reads the plan's d_send / max_sends, d_conn_send / n_conns and summary
+ * (d_plan), and the three wire buffers the entries point into: d_wires[w] is
+ * wire w's base (0 plain, 1 deflated, 2 control) and wire_bytes[w] the number
+ * of readable bytes behind it, its encode's payload_bytes.  Both are host
+ * arrays of three, read during the call.  The encodes' GEVWS_OUT_PAD slack is
+ * what lets the aligned 16-byte vector that holds a wire's last byte be loaded.
+ *
+ * d_conn_buf[c], for every connection (a gevws_conn_buf, below):
+ *   - Span placement.  Connection c's span is d_buf[off, off + bytes).  It
+ *     holds the len bytes of its entries d_send[first, first + count) in order,
+ *     back to back.  Every span starts on a 16-byte boundary.  Spans lie in
+ *     connection order.  The pad up to the next span is zeroed.
+ *   - Empty connections.  A connection with count == 0 gets bytes = 0, and off
+ *     is the next span's start (payload_bytes behind the last span).
+ *   - flags is d_conn_send[c].flags, the reserved tail is zero.
+ *   - Entries.  The entries are the first min(d_plan->frames, max_sends).
+ * d_summary: frames = entries gathered, payload_bytes = buffer bytes used, pads
+ * included (what the host copies; a multiple of 16), payload_len = the sum of
+ * len, errors = 0.
+ *   - Capacity.  GEVWS_ERR_CAPACITY when payload_bytes > buf_cap: the summary
+ *     holds the need and nothing else is written.
+ *   - Gates.  A failed d_plan, zero entries, n_conns == 0 or max_sends == 0
+ *     give a zero summary; nothing else is read or written.
+ *   - Malformed input makes the call GEVWS_ERR_INVALID on the device: `errors`
+ *     counts the bad records (an entry or a connection counts once, whatever is
+ *     wrong with it), the other fields are zero and nothing else is written.
+ *     Every value is checked before it forms an address.  A bad entry has
+ *     wire > 2, off + len beyond that wire's readable bytes (or overflowing),
+ *     conn >= n_conns, or lies outside its connection's [first, first + count).
+ *     A bad connection has a range beyond the entry count, a range that
+ *     overlaps or precedes the previous connection's, or `bytes` not equal to
+ *     the sum of its entries' len (the sum is taken over the entries that name
+ *     the connection and are not bad themselves).
+ *   - Invalid calls.  A non-zero `flags` is GEVWS_ERR_INVALID from the call,
+ *     before any device is touched, even with every pointer NULL.  So is a
+ *     wire base or a d_buf that is not 16-byte aligned, and max_sends >= 2^32.
+ *   - Mapped host memory.  d_buf may be mapped host memory
+ *     (gevws_pinned_alloc).  Every byte of [0, payload_bytes) is written exactly
+ *     once, by an aligned 16-byte store; no byte at or past payload_bytes is
+ *     written.  Of the wires only aligned vectors that hold a byte of an entry
+ *     are loaded. */
+typedef struct gevws_conn_buf {    /* 32 bytes per connection */
+    uint64_t off;      /* its span: d_buf[off, off + bytes), off % 16 == 0 */
+    uint64_t bytes;    /* d_conn_send[c].bytes */
+    uint32_t flags;    /* GEVWS_CTL_*, copied from d_conn_send[c].flags */
+    uint32_t reserved[3];
+} gevws_conn_buf;
+int gevws_send_gather_async(gevws_ctx *ctx, void *stream, const gevws_send *d_send, uint64_t max_sends,
+                            const gevws_conn_send *d_conn_send, uint32_t n_conns, const gevws_summary *d_plan,
+                            const uint8_t *const d_wires[3], const uint64_t wire_bytes[3], uint32_t flags,
+                            uint8_t *d_buf, uint64_t buf_cap, gevws_conn_buf *d_conn_buf,
+                            gevws_summary *d_summary);
+
 /* Measurement helper, not on the reference path: n bytes (n % 16 == 0, d_dst
  * 16-byte aligned, d_src any alignment) copied with the unmask kernel's
  * streaming access pattern minus the XOR and frame lookup -- the achievable
