@@ -34,6 +34,7 @@ from ._abi import CARRY_COMPRESSED, CARRY_KEEP_COMPRESSED, CARRY_LOST, CARRY_OPE
 from ._abi import HANDLER_ECHO_BINARY, HANDLER_ECHO_TEXT, HANDLER_NONE
 from ._abi import (CONTROL_NO_PING_FOR_PONG, CTL_FAILED, CTL_SHUTDOWN, MSG_ERR_CLOSED, WIRE_CONTROL, WIRE_DEFLATED,
                    WIRE_PLAIN)
+from ._abi import ROOM_NONE, ROOMS_SKIP_SENDER
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
                    SUMMARY_UNORDERED, TILE, Header)
@@ -429,6 +430,9 @@ class Responses:
     send_buf: Optional["object"] = None           # uint8, cut to the gather's payload_bytes
     conn_buf: Optional[np.ndarray] = None         # CONN_BUF_DTYPE [n_conns]
     gather_summary: Optional[np.ndarray] = None   # SUMMARY_DTYPE: the gather's
+    # from Engine.broadcast: message m's index in the plain list / the deflate list or -1 (echo.reply_of: the plain one)
+    plain_of: Optional[np.ndarray] = None
+    def_of: Optional[np.ndarray] = None
 
     def summary_host(self) -> np.ndarray:
         return self.summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
@@ -456,6 +460,49 @@ class Responses:
         first, count = int(cs["first"]), int(cs["count"])
         return b"".join(wires[int(e["wire"])][int(e["off"]): int(e["off"]) + int(e["len"])].tobytes()
                         for e in send[first: first + count])
+
+
+@dataclass
+class Rooms:
+    """The room tables of gevws_reply_rooms_async / gevws_room_plan_async, owned
+    by the host as the reference's server owns `sessions`: conn_room[c] is
+    connection c's room or ROOM_NONE, room_first / room_members its inverse in
+    CSR form (int32 device tensors holding the uint32 values)."""
+    conn_room: "object"      # [n_conns]
+    room_first: "object"     # [n_rooms + 1]
+    room_members: "object"   # [n_members]
+    n_rooms: int
+
+    @property
+    def n_members(self) -> int:
+        return int(self.room_members.numel())
+
+    @staticmethod
+    def csr(conn_room, n_rooms: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, int]:
+        """(room_first, room_members, n_rooms) of a conn_room array, on the
+        host: a stable argsort keeps a room's members in increasing order."""
+        cr = np.asarray(conn_room, dtype=np.uint32).reshape(-1)
+        has = np.flatnonzero(cr != ROOM_NONE)
+        if n_rooms is None:
+            n_rooms = int(cr[has].max()) + 1 if has.size else 0
+        if has.size and int(cr[has].max()) >= n_rooms:
+            raise ValueError("Rooms: a room id is not below n_rooms")
+        members = has[np.argsort(cr[has], kind="stable")].astype(np.uint32)
+        first = np.zeros(n_rooms + 1, np.uint32)
+        first[1:] = np.cumsum(np.bincount(cr[has], minlength=n_rooms))[:n_rooms]
+        return first, members, n_rooms
+
+    @classmethod
+    def from_conn_room(cls, conn_room, device, n_rooms: Optional[int] = None) -> "Rooms":
+        torch = _torch()
+        cr = np.ascontiguousarray(np.asarray(conn_room, dtype=np.uint32).reshape(-1))
+        first, members, n_rooms = cls.csr(cr, n_rooms)
+        up = lambda a: torch.from_numpy(a.view(np.int32).copy()).to(device)  # noqa: E731
+        return cls(conn_room=up(cr), room_first=up(first), room_members=up(members), n_rooms=n_rooms)
+
+    def host(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        h = lambda t: t.cpu().numpy().view(np.uint32)  # noqa: E731
+        return h(self.conn_room), h(self.room_first), h(self.room_members)
 
 
 class _DevAddr:
@@ -1321,6 +1368,140 @@ class Engine:
                          send=send, conn_send=conn_send, summary=plan_sum, n_conns=n_conns, send_buf=send_buf,
                          conn_buf=conn_buf, gather_summary=gsum)
 
+    def reply_rooms_async(self, bodies, max_messages: int, msg_summary, join_summary, policy: int, conn_ext,
+                          window_bits, n_conns: int, rooms: "Rooms", flags: int, def_msgs, def_conn, def_summary,
+                          plain, plain_conn, plain_summary, plain_of, def_of, stream=None) -> None:
+        """gevws_reply_rooms_async on device tensors: every delivered body once
+        in the plain list and once in the deflate list, as its room's members
+        need it (flags: ROOMS_SKIP_SENDER)."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        st = lib.gevws_reply_rooms_async(
+            self._ctx, _stream_handle(stream), ptr(bodies), max_messages, ptr(msg_summary), ptr(join_summary), policy,
+            ptr(conn_ext), ptr(window_bits), n_conns, ptr(rooms.conn_room), ptr(rooms.room_first),
+            ptr(rooms.room_members), rooms.n_rooms, rooms.n_members, flags, ptr(def_msgs), ptr(def_conn),
+            ptr(def_summary), ptr(plain), ptr(plain_conn), ptr(plain_summary), ptr(plain_of), ptr(def_of))
+        if st != OK:
+            raise RuntimeError(f"gevws_reply_rooms_async: {status_string(st)}")
+
+    def room_plan_async(self, max_frames: int, decoded, conn_out, n_conns: int, msg_of, msg_end, plain_of, def_of,
+                        max_messages: int, msg_summary, join_summary, conn_ext, ctl_of, conn_ctl, ctl_summary,
+                        plain_off, plain_encoded, def_off, def_encoded, ctl_off, ctl_encoded, rooms: "Rooms",
+                        flags: int, send, max_sends: int, conn_send, summary, stream=None) -> None:
+        """gevws_room_plan_async on device tensors: the send plan with every
+        published frame named once per recipient of its room."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        st = lib.gevws_room_plan_async(
+            self._ctx, _stream_handle(stream), max_frames, ptr(decoded), ptr(conn_out), n_conns, ptr(msg_of),
+            ptr(msg_end), ptr(plain_of), ptr(def_of), max_messages, ptr(msg_summary), ptr(join_summary),
+            ptr(conn_ext), ptr(ctl_of), ptr(conn_ctl), ptr(ctl_summary), ptr(plain_off), ptr(plain_encoded),
+            ptr(def_off), ptr(def_encoded), ptr(ctl_off), ptr(ctl_encoded), ptr(rooms.conn_room),
+            ptr(rooms.room_first), ptr(rooms.room_members), rooms.n_rooms, rooms.n_members, flags, ptr(send),
+            max_sends, ptr(conn_send), ptr(summary))
+        if st != OK:
+            raise RuntimeError(f"gevws_room_plan_async: {status_string(st)}")
+
+    def broadcast(self, out: "Batch", msgs: "Messages", bodies: "Bodies", policy: int, conn_ext, rooms: "Rooms",
+                  window_bits=None, flags: int = 0, rooms_flags: int = 0, control_flags: int = 0,
+                  gather: bool = False, stream=None) -> "Responses":
+        """Everything a pass sends when a message goes to its sender's room:
+        control -> reply_rooms -> deflate -> the three encodes -> room plan ->
+        (gather).  The arguments are respond's, without contexts (a broadcast
+        payload is shared, so no connection's window can hold it); rooms: the
+        room tables, rooms_flags: ROOMS_SKIP_SENDER or 0, flags: the deflate
+        step's.  The result is respond's: conn_bytes(c) and host_sends() work
+        unchanged; echo.def_conn / echo.plain_conn name the senders."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        n_conns, nf, nm = out.n_conns, msgs.n_frames, bodies.n_messages
+        if out.aux_slots < n_conns:
+            raise ValueError(f"broadcast: the batch reserves {out.aux_slots} aux slots for {n_conns} connections")
+        aux_cap = _abi.AUX_SLOT * out.aux_slots
+        aux_off = (out.payload.numel() - 16 - aux_cap) // 16 * 16
+        z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        host = lambda t: t.cpu().numpy().view(SUMMARY_DTYPE)[0]  # noqa: E731
+        capf, capm, capc = max(nf, 1), max(nm, 1), max(n_conns, 1)
+        ctl, ctl_conn, ctl_sum = z(capf, 32), z(capf, dt=torch.int32), z(64)
+        ctl_of = torch.full((capf,), -1, dtype=torch.int64, device=dev)
+        msg_end = torch.full((capm,), -1, dtype=torch.int64, device=dev)
+        conn_ctl = z(capc, 32)
+        conn_ctl.view(torch.int64)[:, 0] = -1  # no cut
+        self.control_async(out.frames, nf, out.conn_out, n_conns, out.summary, out.payload, aux_off, aux_cap,
+                           msgs.msg_of, msgs.messages, nm, msgs.conn_msg, msgs.summary, bodies.bodies, bodies.summary,
+                           control_flags, ctl, ctl_conn, ctl_of, msg_end, conn_ctl, ctl_sum, stream)
+        def_msgs, def_conn, def_sum = z(capm, 24), z(capm, dt=torch.int32), z(64)
+        plain, plain_conn, plain_sum = z(capm, 32), z(capm, dt=torch.int32), z(64)
+        plain_of = torch.full((capm,), -1, dtype=torch.int64, device=dev)
+        def_of = torch.full((capm,), -1, dtype=torch.int64, device=dev)
+        self.reply_rooms_async(bodies.bodies, nm, msgs.summary, bodies.summary, policy, conn_ext, window_bits, n_conns,
+                               rooms, rooms_flags, def_msgs, def_conn, def_sum, plain, plain_conn, plain_sum, plain_of,
+                               def_of, stream)
+        torch.cuda.synchronize(self.device)
+        cs, ds, ps = host(ctl_sum), host(def_sum), host(plain_sum)
+        if int(cs["status"]) != OK:
+            raise RuntimeError(f"broadcast: control: {status_string(int(cs['status']))} ({int(cs['errors'])})")
+        if int(ds["status"]) != OK or int(ps["status"]) != OK:
+            raise RuntimeError(f"broadcast: reply_rooms: {status_string(int(ds['status']))} ({int(ds['errors'])} records)")
+        nd, npl, nr = int(ds["frames"]), int(ps["frames"]), int(cs["frames"])
+        src_bytes = int(bodies.summary_host()["payload_bytes"]) if nm else 0
+        dm = def_msgs[:nd].cpu().numpy().reshape(-1).view(DEFLATE_MSG_DTYPE)
+        dcap = int(sum((deflate_bound(int(x)) + 15) // 16 * 16 for x in dm["length"])) + 16
+        res = Deflated(frames=z(capm, 32), out=torch.empty(dcap + _abi.OUT_PAD, dtype=torch.uint8, device=dev),
+                       summary=z(64), n_messages=nd)
+        if nm:
+            self.deflate_async(def_msgs, nm, def_sum, bodies.out, src_bytes, flags, res.frames, res.out, dcap,
+                               res.summary, stream)
+            torch.cuda.synchronize(self.device)
+        s = res.summary_host()
+        if int(s["status"]) != OK:
+            raise RuntimeError(f"broadcast: deflate: {status_string(int(s['status']))}")
+        lens = lambda recs, k: int(recs[:k].cpu().numpy().reshape(-1).view(OUT_FRAME_DTYPE)["payload_len"].sum())  # noqa: E731
+        wires, tables = [], []
+        for recs, cap, gate, payload, k, total in (
+                (plain, capm, plain_sum, bodies.out if nm else out.payload, npl, lens(plain, npl)),
+                (res.frames, capm, res.summary, res.out, nd, int(s["payload_len"])),
+                (ctl, capf, ctl_sum, out.payload, nr, lens(ctl, nr))):
+            wcap = total + 14 * k + 16
+            wire = torch.empty(wcap + _abi.OUT_PAD, dtype=torch.uint8, device=dev)
+            off, esum = torch.zeros(cap, dtype=torch.int64, device=dev), z(64)
+            self.encode_replies_async(recs, cap, gate, payload, wire, wcap, off, esum, stream)
+            torch.cuda.synchronize(self.device)
+            es = host(esum)
+            if int(es["status"]) != OK:
+                raise RuntimeError(f"broadcast: encode: {status_string(int(es['status']))}")
+            wires.append((wire[: int(es["payload_bytes"])], off[:k].cpu().numpy().astype(np.uint64)))
+            tables.append((off, esum))
+        (plain_off, plain_enc), (def_off, def_enc), (ctl_off, ctl_enc) = tables
+        conn_send, plan_sum = z(capc, 32), z(64)
+        max_sends = capf
+        for attempt in range(2):
+            send = z(max(max_sends, 1), 32)
+            self.room_plan_async(nf, out.summary, out.conn_out, n_conns, msgs.msg_of, msg_end, plain_of, def_of, nm,
+                                 msgs.summary, bodies.summary, conn_ext, ctl_of, conn_ctl, ctl_sum, plain_off,
+                                 plain_enc, def_off, def_enc, ctl_off, ctl_enc, rooms, rooms_flags, send, max_sends,
+                                 conn_send, plan_sum, stream)
+            torch.cuda.synchronize(self.device)
+            pls = host(plan_sum)
+            if int(pls["status"]) == ERR_CAPACITY and attempt == 0:   # a fan-out: more entries than frames
+                max_sends = int(pls["frames"])
+                continue
+            break
+        if int(pls["status"]) != OK:
+            raise RuntimeError(f"broadcast: plan: {status_string(int(pls['status']))} ({int(pls['errors'])})")
+        echo = Echo(def_wire=wires[1][0], def_conn=def_conn[:nd].cpu().numpy().view(np.uint32), def_off=wires[1][1],
+                    plain_wire=wires[0][0], plain_conn=plain_conn[:npl].cpu().numpy().view(np.uint32),
+                    plain_off=wires[0][1], reply_of=plain_of[:nm].cpu().numpy(), deflated=res)
+        send_buf = conn_buf = gsum = None
+        if gather:
+            send_buf, conn_buf, gsum = self._gather(send, max_sends, conn_send, n_conns, plan_sum,
+                                                    int(pls["payload_bytes"]),
+                                                    (wires[0][0], wires[1][0], wires[2][0]), stream)
+        return Responses(echo=echo, ctl_wire=wires[2][0], ctl_conn=ctl_conn[:nr].cpu().numpy().view(np.uint32),
+                         ctl_of=ctl_of[:nf].cpu().numpy(), msg_end=msg_end[:nm].cpu().numpy().view(np.uint64),
+                         conn_ctl=conn_ctl[:n_conns].cpu().numpy().reshape(-1).view(CONN_CTL_DTYPE), ctl_summary=cs,
+                         send=send, conn_send=conn_send, summary=plan_sum, n_conns=n_conns, send_buf=send_buf,
+                         conn_buf=conn_buf, gather_summary=gsum, plain_of=plain_of[:nm].cpu().numpy(),
+                         def_of=def_of[:nm].cpu().numpy())
+
     def messages(self, out: "Batch", state=None, max_messages: Optional[int] = None, stream=None, *,
                  conn_ext=None) -> "Messages":
         """The message pass over a decoded batch; `state` (uint8 [n_conns, 8]
@@ -1962,4 +2143,4 @@ __all__ = ["Engine", "Batch", "Comm", "RingBuffer", "Connection", "Protocol", "H
            "DEFLATE_MSG_DTYPE", "DEFLATE_PLAIN_IF_NOT_SMALLER", "DEFLATE_DYNAMIC", "Deflated", "deflate_raw", "deflate_bound",
            "deflate_raw_ctx", "deflate_negotiate_takeover", "DEF_CTX_BYTES", "EXT_SERVER_TAKEOVER",
            "NEGOTIATE_SERVER_TAKEOVER", "Carry", "CARRY_DTYPE", "CARRY_OPEN", "CARRY_LOST",
-           "CARRY_COMPRESSED", "CARRY_KEEP_COMPRESSED"]
+           "CARRY_COMPRESSED", "CARRY_KEEP_COMPRESSED", "Rooms", "ROOM_NONE", "ROOMS_SKIP_SENDER"]

@@ -94,6 +94,9 @@ CONTROL_NO_PING_FOR_PONG = 1  # gevws_control_async flag
 CTL_SHUTDOWN = 1  # gevws_conn_ctl.flags: the connection has a cut
 CTL_FAILED = 2  # beside it: the cut is a failure, close_code was sent
 WIRE_PLAIN, WIRE_DEFLATED, WIRE_CONTROL = 0, 1, 2  # gevws_send.wire
+# rooms (gevws_reply_rooms_async, gevws_room_plan_async)
+ROOM_NONE = 0xFFFFFFFF  # d_conn_room: the connection is in no room
+ROOMS_SKIP_SENDER = 1  # call flag of both: a sender is not sent its own messages
 
 IN_PAD = 64
 MEM_DEFAULT, MEM_FINE, MEM_UNCACHED = 0, 1, 2  # gevws_device_alloc kinds
@@ -370,6 +373,13 @@ SIGNATURES = {
                                              P, P, P, P, P, P, P, P, P, P, P, P, P, ctypes.c_uint64, P, P]),
     "gevws_send_gather_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint32, P, P, P, ctypes.c_uint32,
                                                P, ctypes.c_uint64, P, P]),
+    "gevws_reply_rooms_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, ctypes.c_int, P, P, ctypes.c_uint32,
+                                               P, P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                               P, P, P, P, P, P, P, P]),
+    "gevws_room_plan_async": (ctypes.c_int, [P, P, ctypes.c_uint64, P, P, ctypes.c_uint32, P, P, P, P,
+                                             ctypes.c_uint64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                             ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_uint64,
+                                             P, P]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),
     "gevws_synth_async": (ctypes.c_int, [P, P, P, P, ctypes.c_uint64, ctypes.c_uint64]),
     "gevws_synth_verify_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P,

@@ -1437,6 +1437,131 @@ int gevws_send_gather_async(gevws_ctx *ctx, void *stream, const gevws_send *d_se
                             uint8_t *d_buf, uint64_t buf_cap, gevws_conn_buf *d_conn_buf,
                             gevws_summary *d_summary);
 
+/* Rooms: a delivered message goes to every connection in its sender's room
+ * (the reference's example/websocket/main.go loops over serv.sessions on the
+ * host).  Additions to ABI version 3: nothing above changes.  The chain of one
+ * pass is the echo chain's with two steps exchanged:
+ *   ... -> control -> gevws_reply_rooms_async -> deflate (no contexts) ->
+ *   the three encodes -> gevws_room_plan_async -> gevws_send_gather_async.
+ * A message is framed once and compressed once; the plan names its bytes once
+ * per recipient, and the gather copies them.
+ *
+ * Room tables.  The caller owns them: device memory, read only.
+ *   - d_conn_room[c] (n_conns entries): connection c's room, < n_rooms, or
+ *     GEVWS_ROOM_NONE.  A connection receives from its room and publishes to
+ *     it; a GEVWS_ROOM_NONE connection publishes nothing and is sent only its
+ *     own control replies.
+ *   - The inverse index in CSR form: d_room_first[n_rooms + 1] and
+ *     d_room_members[n_members].  Room g's members are
+ *     d_room_members[first[g], first[g + 1]), strictly increasing.
+ *   - Well formed means: first[0] == 0; first never decreases; first[n_rooms]
+ *     == n_members <= n_conns; every member < n_conns; members increase
+ *     strictly inside a room; d_conn_room[member] == its room; every
+ *     d_conn_room[c] is < n_rooms or GEVWS_ROOM_NONE; the connections with a
+ *     room number n_members.  The two tables are then a bijection.  n_rooms ==
+ *     0 with every connection GEVWS_ROOM_NONE is well formed.
+ *   - Both calls check this on the device before anything is indexed by the
+ *     tables.  The records are the n_rooms + 1 entries of d_room_first, the
+ *     n_members slots and the n_conns connections; a record counts once,
+ *     whatever is wrong with it, and a wrong number of roomed connections
+ *     counts as one more.  Any bad record makes the call GEVWS_ERR_INVALID on
+ *     the device: `errors` is the count, the other summary fields are zero and
+ *     nothing else is written.
+ *   - A call whose gates leave it no records (below) reads no table.
+ *
+ * Recipient kind.  A connection takes deflate when its d_conn_ext byte has
+ * GEVWS_EXT_DEFLATE and not GEVWS_EXT_SERVER_TAKEOVER; otherwise it takes plain
+ * (d_conn_ext == NULL: every connection).  A server-takeover connection gets a
+ * broadcast message uncompressed, RSV1 clear: RFC 7692 section 6 leaves that
+ * choice to the sender message by message, a message compressed in that
+ * connection's own context could not be shared, and an uncompressed message
+ * stays out of its window.
+ *
+ * gevws_reply_rooms_async is gevws_reply_bodies_async with rooms.
+ *   - Inputs.  That function's, the room tables and `flags`.  policy, the
+ *     bodies looked at, the gates (a failed d_msg_summary or d_join_summary
+ *     gives two zero summaries and nothing else) and the malformed bodies (no
+ *     GEVWS_BODY_JOINED / GEVWS_BODY_INFLATED, conn >= n_conns) are unchanged.
+ *     GEVWS_HANDLER_NONE looks at no body and no table.
+ *   - Flags.  GEVWS_ROOMS_SKIP_SENDER: a sender is not among its message's
+ *     recipients.  Any other bit is GEVWS_ERR_INVALID from the call, before any
+ *     device is touched, even with every pointer NULL.
+ *   - Recipients.  A delivered body of sender c in room g goes to g's members,
+ *     without c under GEVWS_ROOMS_SKIP_SENDER.  The body of a GEVWS_ROOM_NONE
+ *     sender has none.
+ *   - Lists.  The body enters the plain list (d_plain, as the reply step builds
+ *     it: fin 1, rsv 0) exactly when a recipient takes plain, and the deflate
+ *     list (d_def_msgs) exactly when a recipient takes deflate: both, one or
+ *     neither.  d_plain_conn[k] / d_def_conn[k] are the sender.  Both lists
+ *     keep the message order.  d_plain_of[m] / d_def_of[m], for each of the
+ *     bodies, = the index in that list or -1.
+ *   - Window.  window_bits of a deflate-list entry is the smallest effective
+ *     d_conn_window_bits byte among the room's deflate-taking members (0, or a
+ *     NULL table, counts as 15; the sender counts even when skipped), so one
+ *     payload fits every recipient's server_max_window_bits.  The entry holds
+ *     the value itself, 8..15.  A byte outside {0, 8..15} on a deflate-taking
+ *     member makes that member's slot a bad record.
+ *   - Summaries.  frames = the list's count, the other fields zero.  Bad table
+ *     records and malformed bodies add up in `errors` of both.
+ *   - The deflate list is for gevws_deflate_async (no contexts) over the join's
+ *     d_out; the plain list for gevws_encode_replies_async, as in the echo.
+ *
+ * gevws_room_plan_async is gevws_send_plan_async with a fan-out.
+ *   - Inputs.  That function's, with d_plain_of / d_def_of in the place of
+ *     d_reply_of, plus the room tables and the same `flags`.
+ *   - Publishing.  Frame f of sender s publishes when d_ctl_of[f] < 0, m =
+ *     d_msg_of[f] is a message, d_msg_end[m] == f and s has a room: in wire 0
+ *     when d_plain_of[m] >= 0 and in wire 1 when d_def_of[m] >= 0.  The bytes
+ *     are that wire's [off, off + len), as the send plan takes them.
+ *   - Order.  Recipient r, which takes wire w, is sent first every publication
+ *     in wire w of its room's members in frame order (sender order, then stream
+ *     order; r's own left out under GEVWS_ROOMS_SKIP_SENDER), then its own
+ *     control replies in frame order (wire 2).  The close reply of a cut is
+ *     therefore the last thing r is sent.
+ *   - Outputs.  d_send / max_sends / d_conn_send / d_summary with the send
+ *     plan's meaning, field for field: an entry is {off, len, frame = the
+ *     publishing frame, conn = r, wire}; `errors` = connections with
+ *     GEVWS_CTL_SHUTDOWN, d_conn_send[c].flags = d_conn_ctl[c].flags.
+ *     gevws_send_gather_async runs over them unchanged.
+ *   - Capacity, gates.  GEVWS_ERR_CAPACITY when there are more entries than
+ *     max_sends: frames (and payload_bytes) hold the need and nothing else is
+ *     written.  A failed d_decoded, d_msg_summary, d_join_summary,
+ *     d_ctl_summary or encode summary, no decoded frames, n_conns == 0 or
+ *     max_frames == 0 give a zero summary; nothing else is read or written.
+ *   - Malformed input.  A reply index outside its list's count, a d_msg_of
+ *     entry outside the message table, a frame that would send something and
+ *     belongs to no connection or an offset table that decreases makes the
+ *     call GEVWS_ERR_INVALID on the device, and so do bad room records:
+ *     `errors` counts the frames and the records, the other fields are zero
+ *     and nothing else is written.  Every index is checked before it is used.
+ *   - Invalid calls.  A flag bit other than GEVWS_ROOMS_SKIP_SENDER or
+ *     max_sends >= 2^32 is GEVWS_ERR_INVALID from the call, before any device
+ *     is touched, even with every pointer NULL. */
+#define GEVWS_ROOM_NONE 0xFFFFFFFFu
+#define GEVWS_ROOMS_SKIP_SENDER 1u   /* call flag of both */
+int gevws_reply_rooms_async(gevws_ctx *ctx, void *stream, const gevws_body *d_bodies, uint64_t max_messages,
+                            const gevws_summary *d_msg_summary, const gevws_summary *d_join_summary, int policy,
+                            const uint8_t *d_conn_ext /* may be NULL */,
+                            const uint8_t *d_conn_window_bits /* may be NULL: 15 */, uint32_t n_conns,
+                            const uint32_t *d_conn_room, const uint32_t *d_room_first,
+                            const uint32_t *d_room_members, uint32_t n_rooms, uint32_t n_members, uint32_t flags,
+                            gevws_deflate_msg *d_def_msgs, uint32_t *d_def_conn, gevws_summary *d_def_summary,
+                            gevws_out_frame *d_plain, uint32_t *d_plain_conn, gevws_summary *d_plain_summary,
+                            int64_t *d_plain_of, int64_t *d_def_of);
+int gevws_room_plan_async(gevws_ctx *ctx, void *stream, uint64_t max_frames, const gevws_summary *d_decoded,
+                          const gevws_conn_out *d_conn_out, uint32_t n_conns, const int64_t *d_msg_of,
+                          const uint64_t *d_msg_end, const int64_t *d_plain_of, const int64_t *d_def_of,
+                          uint64_t max_messages, const gevws_summary *d_msg_summary,
+                          const gevws_summary *d_join_summary, const uint8_t *d_conn_ext /* may be NULL */,
+                          const int64_t *d_ctl_of, const gevws_conn_ctl *d_conn_ctl,
+                          const gevws_summary *d_ctl_summary, const uint64_t *d_plain_off,
+                          const gevws_summary *d_plain_encoded, const uint64_t *d_def_off,
+                          const gevws_summary *d_def_encoded, const uint64_t *d_ctl_off,
+                          const gevws_summary *d_ctl_encoded, const uint32_t *d_conn_room,
+                          const uint32_t *d_room_first, const uint32_t *d_room_members, uint32_t n_rooms,
+                          uint32_t n_members, uint32_t flags, gevws_send *d_send, uint64_t max_sends,
+                          gevws_conn_send *d_conn_send, gevws_summary *d_summary);
+
 /* Measurement helper, not on the reference path: n bytes (n % 16 == 0, d_dst
  * 16-byte aligned, d_src any alignment) copied with the unmask kernel's
  * streaming access pattern minus the XOR and frame lookup -- the achievable
