@@ -209,6 +209,37 @@ def deflate_negotiate(value: bytes) -> bytes:
     return out.raw[: n.value]
 
 
+def fragment_records(records: np.ndarray, max_fragment_bytes: int,
+                     max_frags: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """gevws_fragment_records: the fragment step on host records
+    (OUT_FRAME_DTYPE) -> (the fragments, first[n + 1], the summary).  Records
+    longer than max_fragment_bytes become fragments by the rule the device
+    applies.  max_frags: room for this many (None: what is needed).  The
+    step's own failures (ERR_CAPACITY, ERR_INVALID for malformed records) come
+    back in the summary's status, with no fragment and first left as it was
+    (zeros)."""
+    records = np.ascontiguousarray(records, dtype=OUT_FRAME_DTYPE).reshape(-1)
+    n = int(records.size)
+    F = int(max_fragment_bytes)
+    first = np.zeros(n + 1, np.uint64)
+    summary = np.zeros(1, SUMMARY_DTYPE)
+
+    def call(room: int) -> np.ndarray:
+        frags = np.zeros(max(room, 1), OUT_FRAME_DTYPE)
+        st = lib.gevws_fragment_records(records.ctypes.data if n else None, n, F, frags.ctypes.data, room,
+                                        first.ctypes.data, summary.ctypes.data)
+        if st != OK:
+            raise RuntimeError(f"gevws_fragment_records: {status_string(st)}")
+        return frags
+
+    if max_frags is None:  # sized by the step itself: a call with no room reports the need
+        call(0)
+        max_frags = min(int(summary[0]["frames"]), 0xFFFFFFFF)
+    frags = call(int(max_frags))
+    s = summary[0]
+    return frags[: int(s["frames"]) if int(s["status"]) == OK else 0], first, s
+
+
 def _torch():
     import torch
     return torch
@@ -407,6 +438,10 @@ class Echo:
     plain_off: np.ndarray
     reply_of: np.ndarray
     deflated: Optional["Deflated"] = None   # the deflate step's records and payloads
+    # with max_fragment_bytes: reply k's frames in its wire are fragments [first[k], first[k + 1]) of the
+    # list that was encoded (uint64 [replies + 1]); plain_off / def_off stay per reply
+    plain_first: Optional[np.ndarray] = None
+    def_first: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -1161,18 +1196,88 @@ class Engine:
         if st != OK:
             raise RuntimeError(f"gevws_encode_replies_async: {status_string(st)}")
 
+    def fragment_async(self, records, max_records: int, prev, max_fragment_bytes: int, frags, max_frags: int, first,
+                       summary, flags: int = 0, stream=None) -> None:
+        """gevws_fragment_async on device tensors: every record longer than
+        max_fragment_bytes as its fragments in `frags`, first[k] = record k's
+        first fragment (max_records + 1 entries).  prev: the summary of the step
+        that made the records, or None."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        st = lib.gevws_fragment_async(self._ctx, _stream_handle(stream), ptr(records), max_records, ptr(prev),
+                                      max_fragment_bytes, flags, ptr(frags), max_frags, ptr(first), ptr(summary))
+        if st != OK:
+            raise RuntimeError(f"gevws_fragment_async: {status_string(st)}")
+
+    def fragment_offsets_async(self, first, max_records: int, prev, fragged, frag_off, frag_encoded, reply_off,
+                               reply_encoded, stream=None) -> None:
+        """gevws_fragment_offsets_async on device tensors, behind the encode of
+        the fragments: one wire offset per reply and the summary that goes with
+        it, for the send plan or the room plan."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        st = lib.gevws_fragment_offsets_async(self._ctx, _stream_handle(stream), ptr(first), max_records, ptr(prev),
+                                              ptr(fragged), ptr(frag_off), ptr(frag_encoded), ptr(reply_off),
+                                              ptr(reply_encoded))
+        if st != OK:
+            raise RuntimeError(f"gevws_fragment_offsets_async: {status_string(st)}")
+
+    def _fragmented_wire(self, recs, cap: int, gate, payload, k: int, total: int, max_fragment_bytes: int, stream,
+                         who: str):
+        """One record list's wire under a frame size limit: fragment -> encode
+        -> offsets.  cap: the list's capacity, k its count, total its payload
+        bytes.  -> ((the wire, host offsets per reply), (device offsets per
+        reply, their summary), host first[k + 1]); the fragment step's
+        ERR_CAPACITY is retried once from the need."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        F = int(max_fragment_bytes)
+        if F < 1:
+            raise ValueError(f"{who}: max_fragment_bytes must be at least 1")
+        host = lambda t: t.cpu().numpy().view(SUMMARY_DTYPE)[0]  # noqa: E731
+        z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        first, fsum = z(cap + 1, dt=torch.int64), z(64)
+        max_frags = max(k, 1)
+        for attempt in range(2):
+            frags = z(max_frags, 32)
+            self.fragment_async(recs, cap, gate, F, frags, max_frags, first, fsum, 0, stream)
+            torch.cuda.synchronize(self.device)
+            fs = host(fsum)
+            if int(fs["status"]) == ERR_CAPACITY and attempt == 0:
+                max_frags = int(fs["frames"])
+                continue
+            break
+        if int(fs["status"]) != OK:
+            raise RuntimeError(f"{who}: fragment: {status_string(int(fs['status']))} ({int(fs['errors'])})")
+        wcap = total + 14 * int(fs["frames"]) + 16
+        wire = torch.empty(wcap + _abi.OUT_PAD, dtype=torch.uint8, device=dev)
+        frag_off, esum = z(max_frags, dt=torch.int64), z(64)
+        self.encode_replies_async(frags, max_frags, fsum, payload, wire, wcap, frag_off, esum, stream)
+        off, rsum = z(cap, dt=torch.int64), z(64)
+        self.fragment_offsets_async(first, cap, gate, fsum, frag_off, esum, off, rsum, stream)
+        torch.cuda.synchronize(self.device)
+        es, rs = host(esum), host(rsum)
+        if int(es["status"]) != OK or int(rs["status"]) != OK:
+            raise RuntimeError(f"{who}: encode {status_string(int(es['status']))}, offsets "
+                               f"{status_string(int(rs['status']))} ({int(rs['errors'])})")
+        return ((wire[: int(es["payload_bytes"])], off[:k].cpu().numpy().astype(np.uint64)), (off, rsum),
+                first[: k + 1].cpu().numpy().astype(np.uint64))
+
     def echo_messages(self, out: "Batch", msgs: "Messages", bodies: "Bodies", policy: int, conn_ext,
-                      window_bits=None, contexts=None, flags: int = 0, stream=None) -> "Echo":
+                      window_bits=None, contexts=None, flags: int = 0, stream=None,
+                      max_fragment_bytes: Optional[int] = None) -> "Echo":
         """A message-level echo with the lists built on the device: reply ->
         deflate (with contexts: deflate_ctx) -> the two encodes, all on
         `bodies.out`.  conn_ext / window_bits: uint8 [n_conns] device tensors
         (or None), contexts: uint8 [n_conns, DEF_CTX_BYTES] for connections with
         EXT_SERVER_TAKEOVER, flags: the deflate step's.  The bodies come from a
-        join with JOIN_ALL."""
-        return self._echo_chain(out, msgs, bodies, policy, conn_ext, window_bits, contexts, flags, stream)[0]
+        join with JOIN_ALL.  max_fragment_bytes: no frame of a reply carries
+        more payload than this (fragment -> encode -> offsets for each list;
+        Echo.plain_first / def_first name the fragments); None: one frame a
+        reply."""
+        return self._echo_chain(out, msgs, bodies, policy, conn_ext, window_bits, contexts, flags, stream,
+                                max_fragment_bytes)[0]
 
     def _echo_chain(self, out: "Batch", msgs: "Messages", bodies: "Bodies", policy: int, conn_ext, window_bits,
-                    contexts, flags: int, stream):
+                    contexts, flags: int, stream, max_fragment_bytes: Optional[int] = None):
         """echo_messages' chain; beside the Echo, what the send plan reads of it
         on the device: (reply_of, [(offset table, encode summary) of the deflated
         wire, of the plain wire])."""
@@ -1212,12 +1317,18 @@ class Engine:
         s = res.summary_host()
         if int(s["status"]) != OK:
             raise RuntimeError(f"echo_messages: deflate: {status_string(int(s['status']))}")
-        wires, tables = [], []
+        wires, tables, firsts = [], [], [None, None]
         for recs, gate, payload, total in (
                 (res.frames, res.summary, res.out, int(s["payload_len"])),
                 (plain, plain_sum, bodies.out,
                  int(plain[:npl].cpu().numpy().reshape(-1).view(OUT_FRAME_DTYPE)["payload_len"].sum()))):
             k = int(gate.cpu().numpy().view(SUMMARY_DTYPE)[0]["frames"])
+            if max_fragment_bytes is not None:
+                w, t, firsts[len(wires)] = self._fragmented_wire(recs, n, gate, payload, k, total, max_fragment_bytes,
+                                                                 stream, "echo_messages")
+                wires.append(w)
+                tables.append(t)
+                continue
             wcap = total + 14 * k + 16
             wire = torch.empty(wcap + _abi.OUT_PAD, dtype=torch.uint8, device=dev)
             off = torch.zeros(cap, dtype=torch.int64, device=dev)
@@ -1231,7 +1342,8 @@ class Engine:
             tables.append((off, esum))
         return Echo(def_wire=wires[0][0], def_conn=def_conn[:nd].cpu().numpy().view(np.uint32), def_off=wires[0][1],
                     plain_wire=wires[1][0], plain_conn=plain_conn[:npl].cpu().numpy().view(np.uint32),
-                    plain_off=wires[1][1], reply_of=reply_of[:n].cpu().numpy(), deflated=res), reply_of, tables
+                    plain_off=wires[1][1], reply_of=reply_of[:n].cpu().numpy(), deflated=res, plain_first=firsts[1],
+                    def_first=firsts[0]), reply_of, tables
 
     def control_async(self, frames, max_frames: int, conn_out, n_conns: int, decoded, payload, aux_off: int,
                       aux_cap: int, msg_of, messages, max_messages: int, conn_msg, msg_summary, bodies, join_summary,
@@ -1307,7 +1419,7 @@ class Engine:
 
     def respond(self, out: "Batch", msgs: "Messages", bodies: "Bodies", policy: int, conn_ext, window_bits=None,
                 contexts=None, flags: int = 0, control_flags: int = 0, stream=None,
-                gather: bool = False) -> "Responses":
+                gather: bool = False, max_fragment_bytes: Optional[int] = None) -> "Responses":
         """Everything a pass sends: control -> reply -> deflate (with contexts:
         deflate_ctx) -> the three encodes -> plan.  The arguments are
         echo_messages'; control_flags: the control step's.  `bodies` (from a join
@@ -1315,7 +1427,9 @@ class Engine:
         are no longer delivered.  The close bodies go into the aux slots
         alloc_batch reserved, one per connection at the most.  gather=True ends
         the chain with the gather: send_buf / conn_buf / gather_summary hold
-        every connection's bytes in one buffer (Responses.host_sends)."""
+        every connection's bytes in one buffer (Responses.host_sends).
+        max_fragment_bytes: the replies' frame size limit (echo_messages);
+        control replies are never fragmented."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n_conns, nf, nm = out.n_conns, msgs.n_frames, bodies.n_messages
@@ -1338,7 +1452,7 @@ class Engine:
         if int(cs["status"]) != OK:
             raise RuntimeError(f"respond: control: {status_string(int(cs['status']))} ({int(cs['errors'])})")
         echo, reply_of, tables = self._echo_chain(out, msgs, bodies, policy, conn_ext, window_bits, contexts, flags,
-                                                  stream)
+                                                  stream, max_fragment_bytes)
         nr = int(cs["frames"])
         total = int(ctl[:nr].cpu().numpy().reshape(-1).view(OUT_FRAME_DTYPE)["payload_len"].sum())
         wcap = total + 14 * nr + 16
@@ -1402,14 +1516,16 @@ class Engine:
 
     def broadcast(self, out: "Batch", msgs: "Messages", bodies: "Bodies", policy: int, conn_ext, rooms: "Rooms",
                   window_bits=None, flags: int = 0, rooms_flags: int = 0, control_flags: int = 0,
-                  gather: bool = False, stream=None) -> "Responses":
+                  gather: bool = False, stream=None, max_fragment_bytes: Optional[int] = None) -> "Responses":
         """Everything a pass sends when a message goes to its sender's room:
         control -> reply_rooms -> deflate -> the three encodes -> room plan ->
         (gather).  The arguments are respond's, without contexts (a broadcast
         payload is shared, so no connection's window can hold it); rooms: the
         room tables, rooms_flags: ROOMS_SKIP_SENDER or 0, flags: the deflate
         step's.  The result is respond's: conn_bytes(c) and host_sends() work
-        unchanged; echo.def_conn / echo.plain_conn name the senders."""
+        unchanged; echo.def_conn / echo.plain_conn name the senders.
+        max_fragment_bytes: one frame size limit for every recipient (a
+        message is framed once)."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n_conns, nf, nm = out.n_conns, msgs.n_frames, bodies.n_messages
@@ -1455,11 +1571,17 @@ class Engine:
         if int(s["status"]) != OK:
             raise RuntimeError(f"broadcast: deflate: {status_string(int(s['status']))}")
         lens = lambda recs, k: int(recs[:k].cpu().numpy().reshape(-1).view(OUT_FRAME_DTYPE)["payload_len"].sum())  # noqa: E731
-        wires, tables = [], []
+        wires, tables, firsts = [], [], [None, None, None]
         for recs, cap, gate, payload, k, total in (
                 (plain, capm, plain_sum, bodies.out if nm else out.payload, npl, lens(plain, npl)),
                 (res.frames, capm, res.summary, res.out, nd, int(s["payload_len"])),
                 (ctl, capf, ctl_sum, out.payload, nr, lens(ctl, nr))):
+            if max_fragment_bytes is not None and len(wires) < 2:  # (the control replies stay whole)
+                w, t, firsts[len(wires)] = self._fragmented_wire(recs, cap, gate, payload, k, total,
+                                                                 max_fragment_bytes, stream, "broadcast")
+                wires.append(w)
+                tables.append(t)
+                continue
             wcap = total + 14 * k + 16
             wire = torch.empty(wcap + _abi.OUT_PAD, dtype=torch.uint8, device=dev)
             off, esum = torch.zeros(cap, dtype=torch.int64, device=dev), z(64)
@@ -1489,7 +1611,8 @@ class Engine:
             raise RuntimeError(f"broadcast: plan: {status_string(int(pls['status']))} ({int(pls['errors'])})")
         echo = Echo(def_wire=wires[1][0], def_conn=def_conn[:nd].cpu().numpy().view(np.uint32), def_off=wires[1][1],
                     plain_wire=wires[0][0], plain_conn=plain_conn[:npl].cpu().numpy().view(np.uint32),
-                    plain_off=wires[0][1], reply_of=plain_of[:nm].cpu().numpy(), deflated=res)
+                    plain_off=wires[0][1], reply_of=plain_of[:nm].cpu().numpy(), deflated=res,
+                    plain_first=firsts[0], def_first=firsts[1])
         send_buf = conn_buf = gsum = None
         if gather:
             send_buf, conn_buf, gsum = self._gather(send, max_sends, conn_send, n_conns, plan_sum,

@@ -380,6 +380,10 @@ SIGNATURES = {
                                              ctypes.c_uint64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
                                              ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_uint64,
                                              P, P]),
+    "gevws_fragment_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, ctypes.c_uint32, P,
+                                            ctypes.c_uint64, P, P]),
+    "gevws_fragment_offsets_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, P, P, P, P]),
+    "gevws_fragment_records": (ctypes.c_int, [P, ctypes.c_uint64, ctypes.c_uint64, P, ctypes.c_uint64, P, P]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),
     "gevws_synth_async": (ctypes.c_int, [P, P, P, P, ctypes.c_uint64, ctypes.c_uint64]),
     "gevws_synth_verify_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P,

@@ -1562,6 +1562,98 @@ int gevws_room_plan_async(gevws_ctx *ctx, void *stream, uint64_t max_frames, con
                           uint32_t n_members, uint32_t flags, gevws_send *d_send, uint64_t max_sends,
                           gevws_conn_send *d_conn_send, gevws_summary *d_summary);
 
+/* Outbound fragmentation: a frame size limit for what the chain sends (RFC
+ * 6455 section 5.4; the reference writes every message as one frame,
+ * write.go:48-84).  Additions to ABI version 3: nothing above changes.  Two
+ * steps around the encode of a record list (the reply step's d_plain, or the
+ * deflate step's d_out_frames):
+ *   ... -> records -> gevws_fragment_async -> gevws_encode_replies_async over
+ *   d_frags -> gevws_fragment_offsets_async -> the plan (send or room) -> gather.
+ * A reply's fragments are adjacent in the wire, so one plan entry still names
+ * the whole reply; the plans and the gather run unchanged.
+ *
+ * The rule (gev_amd/csrc/gevws_fragment.hpp), for a record r and the limit F =
+ * max_fragment_bytes >= 1, bytes of payload a frame:
+ *   - Splittable.  r splits exactly when hdr.fin == 1, hdr.opcode is 1 or 2,
+ *     hdr.length >= 0, (uint64_t)hdr.length == payload_len and payload_len > F.
+ *     It then has c = ceil(payload_len / F) fragments.
+ *   - Every other record (a control frame, a record that is a fragment already,
+ *     an inconsistent one, an empty or short message) has c = 1: its one
+ *     fragment is the record itself, all 32 bytes.
+ *   - Fragment i of a splittable record: hdr.fin = (i == c - 1); hdr.rsv =
+ *     r's on i == 0, else 0 (RFC 7692 section 6.1: RSV1 on the first fragment
+ *     only); hdr.opcode = r's on i == 0, else 0; hdr.masked and hdr.mask
+ *     copied; hdr.length = payload_len = min(F, L - i F); payload_off =
+ *     r.payload_off + i F.
+ *   - Malformed.  A splittable record with c > 2^31 - 1, and nothing else.
+ *
+ * gevws_fragment_async
+ *   - Records.  The first min(d_prev->frames, max_records) of d_records (d_prev
+ *     == NULL: max_records).  d_prev is the summary of the step that made the
+ *     list: the reply step's d_plain_summary, or the deflate step's.
+ *   - d_frags (max_frags entries, on a 16-byte boundary): the fragments of
+ *     record 0, then of record 1, and so on.  Their payload_off point into the
+ *     payload arena the records pointed into.
+ *   - d_first (max_records + 1 entries): d_first[k] is the index of record k's
+ *     first fragment for k = 0..n, d_first[n] the total.  Entries behind n are
+ *     not written.
+ *   - d_summary: frames = the fragments, payload_len = the sum of their
+ *     payload_len (the records', modulo 2^64), payload_bytes = the records that
+ *     were split, errors = 0, status GEVWS_OK.  It is the d_dispatched of
+ *     gevws_encode_replies_async over d_frags.
+ *   - Capacity.  GEVWS_ERR_CAPACITY when there are more fragments than
+ *     max_frags: the summary holds the same figures (frames is the need) and
+ *     nothing else is written.
+ *   - Gate.  A failed d_prev gives a zero summary; nothing else is read or
+ *     written.
+ *   - Malformed records make the call GEVWS_ERR_INVALID on the device: `errors`
+ *     counts them, the other fields are zero and nothing else is written.
+ *   - Invalid calls.  max_fragment_bytes == 0, any bit of `flags`, max_records
+ *     or max_frags >= 2^32 are GEVWS_ERR_INVALID from the call, before any
+ *     device is touched, even with every pointer NULL.  So is a d_frags that is
+ *     not 16-byte aligned.
+ *   - The step reads no payload byte and forms no address from record data.
+ *
+ * gevws_fragment_offsets_async runs behind the encode of d_frags.
+ *   - Inputs.  d_first / max_records / d_prev as above, d_fragged the fragment
+ *     step's summary, d_frag_off / d_frag_encoded the encode's offset table and
+ *     summary.
+ *   - d_reply_off[k] (max_records entries) = d_frag_off[d_first[k]] for the n
+ *     records (the wire total for a record with no fragment).  d_reply_encoded:
+ *     frames = n, payload_bytes and payload_len the encode's, status GEVWS_OK.
+ *     The two stand where (d_plain_off, d_plain_encoded) or (d_def_off,
+ *     d_def_encoded) stand in gevws_send_plan_async and gevws_room_plan_async:
+ *     entry k's bytes run to the next reply's first fragment, or to the wire
+ *     total.
+ *   - Gates.  A failed d_prev, d_fragged or d_frag_encoded gives a zero summary
+ *     that carries the first failing status (for the encode's
+ *     GEVWS_ERR_CAPACITY also its need in payload_bytes); nothing else is read
+ *     or written.
+ *   - The tables must fit together: d_first[0] == 0, d_first never decreases
+ *     over 0..n, d_first[n] == d_fragged->frames == d_frag_encoded->frames.
+ *     Otherwise the call is GEVWS_ERR_INVALID on the device: `errors` counts the
+ *     bad entries of d_first[0..n] (an entry counts once: 0 for a non-zero
+ *     start, k for d_first[k] > d_first[k + 1], n for a wrong total), the other
+ *     fields are zero and nothing else is written.  d_frag_off is indexed only
+ *     after this check.
+ *   - Invalid calls.  A NULL required pointer or max_records >= 2^32 is
+ *     GEVWS_ERR_INVALID from the call.
+ *
+ * gevws_fragment_records is the fragment step on host memory (FFI callers, CPU
+ * tests): the n records, the same outputs and the same statuses in *summary
+ * (the call itself fails only as an invalid call does). */
+int gevws_fragment_async(gevws_ctx *ctx, void *stream, const gevws_out_frame *d_records, uint64_t max_records,
+                         const gevws_summary *d_prev /* may be NULL: max_records */, uint64_t max_fragment_bytes,
+                         uint32_t flags, gevws_out_frame *d_frags, uint64_t max_frags,
+                         uint64_t *d_first /* max_records + 1 entries */, gevws_summary *d_summary);
+int gevws_fragment_offsets_async(gevws_ctx *ctx, void *stream, const uint64_t *d_first, uint64_t max_records,
+                                 const gevws_summary *d_prev /* may be NULL */, const gevws_summary *d_fragged,
+                                 const uint64_t *d_frag_off, const gevws_summary *d_frag_encoded,
+                                 uint64_t *d_reply_off /* max_records entries */,
+                                 gevws_summary *d_reply_encoded);
+int gevws_fragment_records(const gevws_out_frame *records, uint64_t n, uint64_t max_fragment_bytes,
+                           gevws_out_frame *frags, uint64_t max_frags, uint64_t *first, gevws_summary *summary);
+
 /* Measurement helper, not on the reference path: n bytes (n % 16 == 0, d_dst
  * 16-byte aligned, d_src any alignment) copied with the unmask kernel's
  * streaming access pattern minus the XOR and frame lookup -- the achievable
