@@ -77,6 +77,8 @@ CONN_SEND_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("bytes", "<u8")
 assert CONN_CTL_DTYPE.itemsize == 32 and SEND_DTYPE.itemsize == 32 and CONN_SEND_DTYPE.itemsize == 32
 CONN_BUF_DTYPE = np.dtype([("off", "<u8"), ("bytes", "<u8"), ("flags", "<u4"), ("reserved", "<u4", (3,))])
 assert CONN_BUF_DTYPE.itemsize == 32
+ROOM_CHANGE_DTYPE = np.dtype([("conn", "<u4"), ("room", "<u4")])   # gevws_room_change
+assert ROOM_CHANGE_DTYPE.itemsize == 8
 assert DEFLATE_MSG_DTYPE.itemsize == 24 and OUT_FRAME_DTYPE.itemsize == 32
 assert MSG_STATE_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 32 and CONN_MSG_DTYPE.itemsize == 32
 assert SUMMARY_DTYPE.itemsize == 64 and SYNTH_DTYPE.itemsize == 24
@@ -502,7 +504,9 @@ class Rooms:
     """The room tables of gevws_reply_rooms_async / gevws_room_plan_async, owned
     by the host as the reference's server owns `sessions`: conn_room[c] is
     connection c's room or ROOM_NONE, room_first / room_members its inverse in
-    CSR form (int32 device tensors holding the uint32 values)."""
+    CSR form (int32 device tensors holding the uint32 values).  from_conn_room
+    builds them on the host; build / update make them on the device
+    (gevws_rooms_update_async), so they can stay there from pass to pass."""
     conn_room: "object"      # [n_conns]
     room_first: "object"     # [n_rooms + 1]
     room_members: "object"   # [n_members]
@@ -538,6 +542,75 @@ class Rooms:
     def host(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         h = lambda t: t.cpu().numpy().view(np.uint32)  # noqa: E731
         return h(self.conn_room), h(self.room_first), h(self.room_members)
+
+    @staticmethod
+    def _updated(engine: "Engine", conn_room, n_rooms: int, changes, closed, stream, what: str) -> "Rooms":
+        """gevws_rooms_update_async over the device tensor conn_room: new
+        tables in tensors of their own."""
+        torch = _torch()
+        dev = torch.device("cuda", engine.device)
+        n_conns = int(conn_room.numel())
+        d_changes, n_changes = None, 0
+        if changes is not None:
+            if isinstance(changes, torch.Tensor):   # gevws_room_change records in device memory
+                nbytes = changes.numel() * changes.element_size()
+                if nbytes % 8 or not changes.is_contiguous():
+                    raise ValueError(f"{what}: changes: a contiguous tensor of 8-byte {{conn, room}} records")
+                d_changes, n_changes = changes, nbytes // 8
+            else:
+                ch = np.asarray(changes)
+                if ch.dtype != ROOM_CHANGE_DTYPE:
+                    if ch.size and (ch.ndim != 2 or ch.shape[1] != 2 or ch.dtype.kind not in "iu"):
+                        raise ValueError(f"{what}: changes: ROOM_CHANGE_DTYPE records or an (n, 2) integer array")
+                    if ch.size and (ch.min() < 0 or ch.max() > 0xFFFFFFFF):
+                        raise ValueError(f"{what}: changes: a value outside 32 bits")
+                    ch = np.ascontiguousarray(ch.reshape(-1, 2).astype(np.uint32)).view(ROOM_CHANGE_DTYPE)
+                ch = np.ascontiguousarray(ch.reshape(-1))
+                n_changes = int(ch.shape[0])
+                if n_changes:
+                    d_changes = torch.from_numpy(ch.view(np.uint8).copy()).to(dev)
+        conn_send = plan_summary = None
+        if closed is not None:
+            if closed.n_conns != n_conns:
+                raise ValueError(f"{what}: closed is a pass of {closed.n_conns} connections, the rooms have {n_conns}")
+            conn_send, plan_summary = closed.conn_send, closed.summary
+        out = torch.empty(max(n_conns, 1), dtype=torch.int32, device=dev)
+        first = torch.empty(n_rooms + 1, dtype=torch.int32, device=dev)
+        members = torch.empty(max(n_conns, 1), dtype=torch.int32, device=dev)
+        summary = torch.zeros(64, dtype=torch.uint8, device=dev)
+        engine.rooms_update_async(conn_room if n_conns else None, n_conns, n_rooms, d_changes, n_changes, None,
+                                  conn_send, plan_summary, 0, out, first, members, summary, stream)
+        torch.cuda.synchronize(engine.device)
+        s = summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
+        if int(s["status"]) != OK:
+            raise RuntimeError(f"{what}: {status_string(int(s['status']))} ({int(s['errors'])} records)")
+        return Rooms(conn_room=out[:n_conns], room_first=first, room_members=members[: int(s["frames"])],
+                     n_rooms=n_rooms)
+
+    @classmethod
+    def build(cls, engine: "Engine", conn_room, n_rooms: int, stream=None) -> "Rooms":
+        """from_conn_room on the device: conn_room (a device tensor of 32-bit
+        room ids, or an array that is uploaded) copied, its CSR inverse built by
+        gevws_rooms_update_async without changes."""
+        torch = _torch()
+        if not isinstance(conn_room, torch.Tensor):
+            cr = np.ascontiguousarray(np.asarray(conn_room, dtype=np.uint32).reshape(-1))
+            conn_room = torch.from_numpy(cr.view(np.int32).copy()).to(torch.device("cuda", engine.device))
+        if conn_room.element_size() != 4 or not conn_room.is_contiguous():
+            raise ValueError("Rooms.build: conn_room: a contiguous tensor of 32-bit room ids")
+        return cls._updated(engine, conn_room.reshape(-1), int(n_rooms), None, None, stream, "Rooms.build")
+
+    def update(self, engine: "Engine", changes=None, closed: Optional["Responses"] = None,
+               n_rooms: Optional[int] = None, stream=None) -> "Rooms":
+        """New tables after membership changes, made on the device
+        (gevws_rooms_update_async); this object stays valid.  changes: {conn,
+        room} records applied in order, the last one of a connection wins, room
+        ROOM_NONE leaves -- a ROOM_CHANGE_DTYPE array or an (n, 2) integer array
+        (uploaded), or a device tensor of such records.  closed: the pass's
+        Responses; every connection it shut down (CTL_SHUTDOWN in its device
+        conn_send) leaves its room, whatever `changes` says.  n_rooms: a larger room space (None: unchanged)."""
+        return self._updated(engine, self.conn_room, self.n_rooms if n_rooms is None else int(n_rooms), changes,
+                             closed, stream, "Rooms.update")
 
 
 class _DevAddr:
@@ -1514,6 +1587,20 @@ class Engine:
         if st != OK:
             raise RuntimeError(f"gevws_room_plan_async: {status_string(st)}")
 
+    def rooms_update_async(self, conn_room_in, n_conns: int, n_rooms: int, changes, max_changes: int, prev,
+                           conn_send, plan_summary, flags: int, conn_room_out, room_first_out, room_members_out,
+                           summary, stream=None) -> None:
+        """gevws_rooms_update_async on device tensors: the changes (and the
+        closes of conn_send) applied to conn_room_in, the new rooms and their
+        CSR inverse written to the three outputs."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        st = lib.gevws_rooms_update_async(
+            self._ctx, _stream_handle(stream), ptr(conn_room_in), n_conns, n_rooms, ptr(changes), max_changes,
+            ptr(prev), ptr(conn_send), ptr(plan_summary), flags, ptr(conn_room_out), ptr(room_first_out),
+            ptr(room_members_out), ptr(summary))
+        if st != OK:
+            raise RuntimeError(f"gevws_rooms_update_async: {status_string(st)}")
+
     def broadcast(self, out: "Batch", msgs: "Messages", bodies: "Bodies", policy: int, conn_ext, rooms: "Rooms",
                   window_bits=None, flags: int = 0, rooms_flags: int = 0, control_flags: int = 0,
                   gather: bool = False, stream=None, max_fragment_bytes: Optional[int] = None) -> "Responses":
@@ -2266,4 +2353,5 @@ __all__ = ["Engine", "Batch", "Comm", "RingBuffer", "Connection", "Protocol", "H
            "DEFLATE_MSG_DTYPE", "DEFLATE_PLAIN_IF_NOT_SMALLER", "DEFLATE_DYNAMIC", "Deflated", "deflate_raw", "deflate_bound",
            "deflate_raw_ctx", "deflate_negotiate_takeover", "DEF_CTX_BYTES", "EXT_SERVER_TAKEOVER",
            "NEGOTIATE_SERVER_TAKEOVER", "Carry", "CARRY_DTYPE", "CARRY_OPEN", "CARRY_LOST",
-           "CARRY_COMPRESSED", "CARRY_KEEP_COMPRESSED", "Rooms", "ROOM_NONE", "ROOMS_SKIP_SENDER"]
+           "CARRY_COMPRESSED", "CARRY_KEEP_COMPRESSED", "Rooms", "ROOM_NONE", "ROOMS_SKIP_SENDER",
+           "ROOM_CHANGE_DTYPE"]

@@ -380,6 +380,8 @@ SIGNATURES = {
                                              ctypes.c_uint64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
                                              ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_uint64,
                                              P, P]),
+    "gevws_rooms_update_async": (ctypes.c_int, [P, P, P, ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_uint64, P, P,
+                                                P, ctypes.c_uint32, P, P, P, P]),
     "gevws_fragment_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, ctypes.c_uint32, P,
                                             ctypes.c_uint64, P, P]),
     "gevws_fragment_offsets_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, P, P, P, P]),

@@ -1562,6 +1562,67 @@ int gevws_room_plan_async(gevws_ctx *ctx, void *stream, uint64_t max_frames, con
                           uint32_t n_members, uint32_t flags, gevws_send *d_send, uint64_t max_sends,
                           gevws_conn_send *d_conn_send, gevws_summary *d_summary);
 
+/* Membership changes on the device: joins, moves, leaves and the pass's closes
+ * applied to d_conn_room, and the CSR inverse rebuilt, on the stream (the
+ * reference edits serv.sessions on the host under a mutex).  Additions to ABI
+ * version 3: nothing above changes.  The room tables can stay resident: the
+ * host uploads the 8-byte change records, or nothing when the only changes are
+ * the closes the plan already left in d_conn_send.
+ *
+ * gevws_rooms_update_async
+ *   - Result.  Connection c's new room starts as d_conn_room_in[c].  The
+ *     changes are then applied in list order: {conn, room} puts conn into room
+ *     (< n_rooms: a join or a move; GEVWS_ROOM_NONE: a leave), and the last
+ *     change that names a connection wins.  With d_conn_send, a connection
+ *     whose d_conn_send[c].flags has GEVWS_CTL_SHUTDOWN ends in
+ *     GEVWS_ROOM_NONE: a close beats a join in the same call.
+ *   - Outputs.  d_conn_room_out (n_conns entries): the new rooms.
+ *     d_room_first_out (n_rooms + 1 entries) and d_room_members_out: their CSR
+ *     inverse, well formed as the room tables above define it -- rooms in
+ *     order, a room's members strictly increasing: the tables a stable sort of
+ *     the roomed connections by room gives.  d_room_members_out must hold
+ *     n_conns entries; those at and behind n_members are not written.  The
+ *     result is bit-exact: it does not depend on the grid, the scheduling or
+ *     the order of any atomic.
+ *   - The change count is max_changes, or min(d_prev->frames, max_changes) with
+ *     d_prev (the summary of whatever made the list).  With d_changes == NULL
+ *     the count is 0.  Without changes and without d_conn_send the call is a
+ *     pure build of the CSR on the device.
+ *   - n_rooms belongs to the call: a larger one than the tables were built
+ *     with grows the room space.  Rooms may be empty.  n_rooms == 0 with every
+ *     connection GEVWS_ROOM_NONE is valid.
+ *   - Gates.  A d_prev or a d_plan_summary (the summary of the plan that wrote
+ *     d_conn_send) whose status is not GEVWS_OK gives a zero summary with that
+ *     status (d_prev's first) and nothing else is written: membership does not
+ *     move for a pass that was not sent.
+ *   - d_summary: frames = n_members, payload_len = the connections whose room
+ *     differs between d_conn_room_in and d_conn_room_out, payload_bytes = the
+ *     changes read, errors = 0, status GEVWS_OK.
+ *   - Malformed input.  A d_conn_room_in[c] that is neither < n_rooms nor
+ *     GEVWS_ROOM_NONE, a change with conn >= n_conns and a change whose room is
+ *     neither < n_rooms nor GEVWS_ROOM_NONE are bad records, one counted per
+ *     record.  Any of them makes the call GEVWS_ERR_INVALID on the device:
+ *     `errors` is the count, the other fields are zero and nothing else is
+ *     written.  Every index is checked before anything is indexed by it.
+ *   - Invalid calls.  A NULL ctx, any bit of `flags` (none is defined), a NULL
+ *     output, d_conn_room_in == NULL with n_conns > 0, d_conn_room_out ==
+ *     d_conn_room_in or max_changes >= 2^32 is GEVWS_ERR_INVALID from the call,
+ *     before any device is touched.
+ *   - The inputs are never written, so a call that failed can be repeated as it
+ *     was (the carry's ping-pong rule): the outputs of one call are the inputs
+ *     of the next. */
+typedef struct gevws_room_change {   /* 8 bytes */
+    uint32_t conn;
+    uint32_t room;                   /* < n_rooms joins / moves, GEVWS_ROOM_NONE leaves */
+} gevws_room_change;
+int gevws_rooms_update_async(gevws_ctx *ctx, void *stream, const uint32_t *d_conn_room_in, uint32_t n_conns,
+                             uint32_t n_rooms, const gevws_room_change *d_changes /* may be NULL */,
+                             uint64_t max_changes, const gevws_summary *d_prev /* may be NULL */,
+                             const gevws_conn_send *d_conn_send /* may be NULL */,
+                             const gevws_summary *d_plan_summary /* may be NULL */, uint32_t flags,
+                             uint32_t *d_conn_room_out, uint32_t *d_room_first_out, uint32_t *d_room_members_out,
+                             gevws_summary *d_summary);
+
 /* Outbound fragmentation: a frame size limit for what the chain sends (RFC
  * 6455 section 5.4; the reference writes every message as one frame,
  * write.go:48-84).  Additions to ABI version 3: nothing above changes.  Two
