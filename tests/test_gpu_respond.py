@@ -14,6 +14,7 @@ from tests import _join_model as jm
 from tests import _messages_model as mm
 from tests import _respond_model as rm
 from tests._helpers import gpu_decode
+from tests._session import host_walk
 
 pytestmark = pytest.mark.gpu
 
@@ -286,41 +287,6 @@ def test_gates_capacity_and_malformed_tables(engine):
 
 
 # ---------------------------------------------------------------------------- 4. end to end
-def host_walk(stream: bytes, deflate: bool, limit: int):
-    """What a host that walks a connection's received frames sends: a list of
-    ("ctl", reply wire bytes) / ("echo", message bytes) / ("fail", close code),
-    and the messages echoed; nothing behind a close or a failure."""
-    out, parts, compressed = [], None, False
-    for f in wo.decode_stream(stream).frames:
-        h = f.header
-        bad_rsv = (h.rsv & 3 or (h.rsv & 4 and (h.opcode & 8 or h.opcode == 0))) if deflate else h.rsv
-        if bad_rsv or (h.opcode & 8 and (not h.fin or h.length > 125)):
-            return out + [("fail", 1002)]
-        if h.opcode & 8:
-            reply, shutdown = wo.on_message(h, f.payload, wo.HANDLER_NONE)
-            out.append(("ctl", reply))
-            if shutdown:
-                return out
-            continue
-        if h.opcode:
-            parts, compressed, text = [], bool(h.rsv & 4), h.opcode == 1
-        parts.append(f.payload)
-        if not h.fin:
-            continue
-        data = b"".join(parts)
-        if compressed:
-            try:
-                data = zlib.decompressobj(-15).decompress(data + b"\x00\x00\xff\xff")
-            except zlib.error:
-                return out + [("fail", 1007)]
-            if len(data) > limit:
-                return out + [("fail", 1009)]
-        if text and not wo.utf8_valid(data):
-            return out + [("fail", 1007)]
-        out.append(("echo", data))
-    return out
-
-
 def test_respond_end_to_end(engine):
     import torch
     rng = np.random.default_rng(0x65326533)
