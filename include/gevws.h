@@ -648,6 +648,9 @@ int gevws_inflate_raw(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap,
  * at ring[i & 32767], bytes never written stay zero.  A slot's content is a
  * function of the connection's stream only, not of how the stream was cut
  * into passes, and gevws_inflate_raw_ctx produces the same bytes on the host.
+ * Behaviour depends on `total` only through min(total, 32 768) and total mod
+ * 32 768: a connection that has inflated 2^32 or 2^62 bytes is served as one
+ * that has inflated 70 000 (the tests relocate slots across those positions).
  * 32 832 bytes a connection: 538 MB of device memory for 16 384 connections.
  *
  * gevws_inflate_ctx_async is gevws_inflate_async plus d_conn_ext (one byte per
@@ -828,7 +831,11 @@ int gevws_deflate_raw_flags(const uint8_t *in, uint64_t n, int window_bits, uint
  * GEVWS_DEFLATE_DYNAMIC does not change it: the tokens are the same) -- not
  * of how the messages were cut into calls, the batch around
  * them, the grid or the pad bytes behind a message in d_src -- and
- * gevws_deflate_raw_ctx produces the same bytes on the host.  41 024 bytes a
+ * gevws_deflate_raw_ctx produces the same bytes on the host.  Behaviour
+ * depends on `total` only through min(total, 32 768) and total mod 65 536 (the
+ * table holds positions mod 65 536): a connection that has sent 2^32 or 2^62
+ * bytes is served as one that has sent 70 000 (the tests relocate slots across
+ * those positions).  41 024 bytes a
  * connection: 672 MB of device memory for 16 384 connections.
  *
  * gevws_deflate_ctx_async is gevws_deflate_async plus d_msg_conn (one

@@ -86,6 +86,14 @@ class Slot:
     def copy(self) -> "Slot":
         return Slot(self.image())
 
+    def relocated(self, shift: int) -> "Slot":
+        """The slot of the same connection `shift` stream bytes later (a
+        multiple of the ring's size): `total` raised, nothing else changed."""
+        assert shift % WIN == 0 and 0 <= self.total + shift < 1 << 64
+        s = self.copy()
+        s.total += shift
+        return s
+
     def window(self) -> bytes:
         n = min(self.total, WIN)
         first = (self.total - n) & (WIN - 1)
@@ -145,6 +153,24 @@ def match3_at_32768() -> bytes:
     w = Bits()
     w.put(0, 1), w.put(1, 2)
     w.lit(257), w.code(29, 5), w.put(8191, 13)
+    w.lit(256)
+    w.put(0, 3)
+    return w.bytes()
+
+
+def match_at(dist: int, length: int = 3) -> bytes:
+    """One fixed block: a match of `length` (3..10) at distance `dist`, end of
+    block, then the sync flush's empty stored block minus its tail."""
+    assert 3 <= length <= 10 and 1 <= dist <= 32768
+    w = Bits()
+    w.put(0, 1), w.put(1, 2)
+    w.lit(254 + length)
+    y = dist - 1
+    if y < 4:
+        w.code(y, 5)
+    else:
+        e = y.bit_length() - 2
+        w.code(2 * e + 2 + ((y >> e) & 1), 5), w.put(y & ((1 << e) - 1), e)
     w.lit(256)
     w.put(0, 3)
     return w.bytes()

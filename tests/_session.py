@@ -853,6 +853,116 @@ def run_session(engine, conns: Sequence[Conn], cuts, passes: int, F: Optional[in
     return run
 
 
+LEAD_FILL = 0xA5
+LEAD_FILLED = 1 << 20
+
+
+def lead_header(length: int) -> bytes:
+    """An unmasked FIN frame's header, the reserved opcode 0x3, the 64-bit length form."""
+    return bytes([0x83, 127]) + length.to_bytes(8, "big")
+
+
+@dataclass
+class FarRun:
+    """run_far_session's result; connection 0 is the leading one everywhere."""
+    sent: List[bytes]                   # [conn]: the bytes of the send plan
+    gathered: List[bytes]               # [conn]: the bytes of the gather
+    conn_flags: np.ndarray              # the plan's flags per connection
+    decode_summary: np.ndarray
+    payload_off: np.ndarray             # per frame record
+    first_frame: np.ndarray             # per connection
+    aux_off: int
+    bodies_in_place: np.ndarray         # BODY_DTYPE, the join without JOIN_ALL
+    bodies_copied: np.ndarray           # ... and with it
+    body_bytes: List[Tuple[bytes, bytes]]   # per message: (in place, copied)
+    seconds: float
+
+
+def run_far_session(engine, conns: Sequence[Conn], lead: int, F: Optional[int] = None,
+                    deflate_flags: int = 0) -> FarRun:
+    """One pass of run_session's chain behind a payload arena larger than 4 GiB:
+    connection 0 holds one unmasked frame of `lead` payload bytes with a
+    reserved opcode (a protocol error: it is sent a 1002 close and nothing
+    else), so every payload offset of `conns` behind it, and the aux region
+    at the arena's end, lie `lead` bytes up.  The input is assembled on the
+    device: the frame's payload is whatever the allocation holds but for its
+    first MiB, LEAD_FILL -- where an offset cut to 32 bits would land.
+
+    decode -> messages -> inflate -> join -> respond, gathered, as run_session
+    with one pass and without a carry (nothing spans passes; the calls are then
+    their NULL-carry forms bit for bit), the capacities those of the session
+    without the leading frame.  The join runs twice, without GEVWS_JOIN_ALL
+    first: the reply step takes copied bodies only (include/gevws.h), so the
+    bodies left in place in the far arena are read back here instead."""
+    import time
+
+    import torch
+
+    import gev_amd
+    from tests._messages_model import _dev
+    t0 = time.perf_counter()
+    dev = torch.device("cuda", engine.device)
+    n = len(conns) + 1
+    rest = np.frombuffer(b"".join(c.wire for c in conns), np.uint8)
+    head = lead_header(lead)
+    in_bytes = len(head) + lead + rest.size
+    d_in = torch.empty(in_bytes + gev_amd.IN_PAD, dtype=torch.uint8, device=dev)
+    d_in[: len(head)] = torch.from_numpy(np.frombuffer(head, np.uint8).copy()).to(dev)
+    d_in[len(head): len(head) + LEAD_FILLED] = LEAD_FILL
+    d_in[len(head) + lead: in_bytes] = torch.from_numpy(rest.copy()).to(dev)
+    d_in[in_bytes:] = 0
+    lens = np.array([len(head) + lead] + [len(c.wire) for c in conns], np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    n_frames = 1 + sum(len(c.frames) for c in conns)
+    lead16 = (lead + 15) // 16 * 16
+    near_cap = int(rest.size) + 16 * n_frames + 64
+    batch = engine.decode(d_in, in_bytes, torch.from_numpy(np.stack([offs, lens], 1)).to(dev), n,
+                          max_frames=n_frames, payload_cap=lead16 + near_cap, aux_slots=n)
+    del d_in
+    co = batch.conn_out_host()
+    assert not (co["status"] < 0).any() and int(co["consumed"][0]) == int(lens[0])
+    ds = batch.summary_host().copy()
+    ext = _dev(np.array([0] + [c.ext for c in conns], np.uint8), dev, 1)
+    wb = _dev(np.array([0] + [c.window_bits for c in conns], np.uint8), dev, 1)
+    state = torch.zeros((n, 8), dtype=torch.uint8, device=dev)
+    inf_ctx = torch.zeros((n, gev_amd.INF_CTX_BYTES), dtype=torch.uint8, device=dev)
+    def_ctx = torch.zeros((n, gev_amd.DEF_CTX_BYTES), dtype=torch.uint8, device=dev)
+    msgs = engine.messages(batch, state, conn_ext=ext)
+    nm = int(msgs.summary_host()["frames"])
+    inf = engine.inflate(batch, msgs, LIMIT, state, out_cap=4 * near_cap + 16 * nm, conn_ext=ext, contexts=inf_ctx)
+    join_cap = (int(inf.summary_host()["payload_bytes"]) + 15) // 16 * 16 + near_cap
+    in_place = engine.join(batch, msgs, inf, flags=0, out_cap=join_cap)
+    bodies = engine.join(batch, msgs, inf, flags=gev_amd.JOIN_ALL, out_cap=join_cap)
+    b0, b1 = in_place.bodies_host().copy(), bodies.bodies_host().copy()
+    o0, o1 = in_place.out.cpu().numpy(), bodies.out.cpu().numpy()
+    far = batch.payload[lead16: lead16 + near_cap].cpu().numpy()
+    body_bytes = []
+    for r0, r1 in zip(b0, b1):
+        pair = []
+        for r, out in ((r0, o0), (r1, o1)):
+            off, k, fl = int(r["off"]), int(r["length"]), int(r["flags"])
+            if not fl & gev_amd.BODY_WHOLE:
+                pair.append(b"")
+            elif fl & (gev_amd.BODY_JOINED | gev_amd.BODY_INFLATED):
+                pair.append(out[off: off + k].tobytes())
+            else:
+                assert off >= lead16
+                pair.append(far[off - lead16: off - lead16 + k].tobytes())
+        body_bytes.append(tuple(pair))
+    res = engine.respond(batch, msgs, bodies, gev_amd.HANDLER_ECHO_TEXT, ext, wb, contexts=def_ctx,
+                         flags=deflate_flags, gather=True, max_fragment_bytes=F)
+    sent = all_conn_bytes(res)
+    for c in range(0, n, 37):
+        assert res.conn_bytes(c) == sent[c], c
+    aux_cap = gev_amd._abi.AUX_SLOT * batch.aux_slots
+    return FarRun(sent=sent, gathered=[bytes(m) for m in res.host_sends()],
+                  conn_flags=res.conn_send_host()["flags"].copy(), decode_summary=ds,
+                  payload_off=batch.frames_host()["payload_off"].astype(np.uint64),
+                  first_frame=co["first_frame"].astype(np.int64),
+                  aux_off=(batch.payload.numel() - 16 - aux_cap) // 16 * 16, bodies_in_place=b0, bodies_copied=b1,
+                  body_bytes=body_bytes, seconds=time.perf_counter() - t0)
+
+
 def observed_carries(run: SessionRun, conns: Sequence[Conn], cuts, passes: int) -> Counter:
     """predicted_carries' counts, read from the carry records the run left behind each pass."""
     OPEN, COMPRESSED = 1, 4     # GEVWS_CARRY_OPEN, GEVWS_CARRY_COMPRESSED

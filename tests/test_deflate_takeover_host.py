@@ -16,6 +16,7 @@ import pytest
 import gev_amd
 from gev_amd import _abi
 from tests import _inflate_corpus as ic
+from tests import _takeover_far as far
 from tests import test_deflate_host as base
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -228,6 +229,81 @@ def test_a_takeover_message_needs_its_window():
         assert raised or got != a
         st, got = gev_amd.inflate_raw(second, len(a))
         assert st != 0 or got != a
+
+
+# ---------------------------------------------------------------------------- old connections: relocated slots
+# A connection that has echoed 2 GiB, 4 GiB or far more: tests/_takeover_far.py.  Two references, neither of
+# them the relocated run: zlib with the history as its dictionary, and the same call on the unrelocated slot.
+@pytest.fixture(scope="module")
+def old():
+    """The two old slots per (flags, window_bits) -- `odd` at 70 001 bytes, `edge` at 131 055 -- and their
+    plain history.  (The slot does not depend on the flags; it does on window_bits: the tokens differ.)"""
+    rng = far.rng_of(0x6F6C64)
+    hist = far.history_messages(rng)
+    slots = {}
+    for wb in (9, 12, 15):
+        ctx, d = fresh(), zlib.decompressobj(-wb)
+        for k, m in enumerate(hist):
+            assert d.decompress(gev_amd.deflate_raw_ctx(m, ctx, wb, DYN if k % 2 else 0) + TAIL) == m
+            if k == 2:
+                slots["odd", wb] = bytes(ctx)
+        slots["edge", wb] = bytes(ctx)
+        check_slot(ctx, b"".join(hist))
+    assert far.DefSlot(slots["odd", 15]).total == 70001 and far.DefSlot(slots["edge", 15]).total == 131055
+    return dict(slots=slots, hist={"odd": b"".join(hist[:3]), "edge": b"".join(hist)})
+
+
+def run_far_chain(slot0: bytes, history: bytes, msgs, shift: int, wb: int, flags: int, near=None, tag=""):
+    """`msgs` one after the other on slot0 relocated by `shift`, each against both references; returns the
+    unrelocated run [(payload, slot after)] for the next shift to share."""
+    if near is None:
+        ctx, near = bytearray(slot0), []
+        for m in msgs:
+            p = gev_amd.deflate_raw_ctx(m, ctx, wb, flags)
+            near.append((p, bytes(ctx)))
+    ctx, stream = far.DefSlot(slot0).relocated(shift), history
+    for k, (m, (p_near, slot_near)) in enumerate(zip(msgs, near)):
+        p = gev_amd.deflate_raw_ctx(m, ctx, wb, flags)
+        # zlib, the history its dictionary (a window of 2^wb bytes reads no further back than the step's reach)
+        d = zlib.decompressobj(-wb, zdict=stream[-(1 << wb):])
+        assert d.decompress(p + TAIL) == m, (tag, k, "zlib with the history as dictionary")
+        assert p == p_near, (tag, k, "payload differs from the unrelocated slot's")
+        far.assert_def_translated(ctx, slot_near, shift, (tag, k))
+        stream += m
+    return near
+
+
+@pytest.mark.parametrize("flags", [0, DYN])
+@pytest.mark.parametrize("wb", [9, 12, 15])
+def test_relocated_slots_cross_every_boundary(old, flags, wb):
+    rng = far.rng_of(0x666172 + wb)
+    slot0, history = old["slots"]["odd", wb], old["hist"]["odd"]
+    cases = far.far_cases(far.DefSlot(slot0).total, far.U_DEF)
+    helped = 0
+    for kind in far.KINDS:
+        # three messages: the second and third run on a slot the code itself wrote at the far position
+        first = far.message(rng, history, kind)
+        msgs = [first, far.message(rng, history + first, far.KINDS[(far.KINDS.index(kind) + 1) % 5], 5000),
+                first[-300:]]
+        assert all(len(m) for m in msgs)
+        near = None
+        for name, shift in cases:
+            near = run_far_chain(slot0, history, msgs, shift, wb, flags, near, (name, kind, wb, flags))
+        helped += kind != "random" and near[0][0] != gev_amd.deflate_raw(first, wb, flags)
+    assert helped == 4                                      # the history was used: the window matters
+
+
+@pytest.mark.parametrize("flags", [0, DYN])
+def test_short_and_empty_messages_right_at_a_boundary(old, flags):
+    rng = far.rng_of(0x65646765)
+    slot0, history = old["slots"]["edge", 15], old["hist"]["edge"]
+    short = history[-4000:-3983]
+    msgs = [short, b"", far.message(rng, history + short, "text"), b"", far.message(rng, history, "runs", 17)]
+    assert len(short) == 17
+    near = None
+    for name, shift in far.edge_cases(far.DefSlot(slot0).total, far.U_DEF):
+        near = run_far_chain(slot0, history, msgs, shift, 15, flags, near, (name, flags))
+    assert len(near[0][0]) < 12 and near[1][0] == b"\x00"   # a match into the history; an empty message
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")

@@ -13,6 +13,7 @@ import pytest
 
 import gev_amd
 from tests import _inflate_corpus as ic
+from tests import _takeover_far as far
 
 pytestmark = pytest.mark.gpu
 
@@ -335,6 +336,119 @@ def test_past_the_grid_threshold(engine):
     msgs = [(c, base[(c + k) % 16][: 8 + (c + 3 * k) % 32], T, 0) for c in range(n_conns) for k in range(8)]
     assert len(msgs) > 8192
     one_call(engine, msgs, ext, fresh(n_conns))
+
+
+# ---------------------------------------------------------------------------- old connections: relocated slots
+def old_slots(rng):
+    """(the `odd` slot at 70 001 bytes, the `edge` slot at 131 055, their histories), made by the host twin."""
+    hist = far.history_messages(rng)
+    ctx = bytearray(CTX)
+    for k, m in enumerate(hist):
+        gev_amd.deflate_raw_ctx(m, ctx, 0, 0)
+        if k == 2:
+            odd = bytes(ctx)
+    return odd, bytes(ctx), b"".join(hist[:3]), b"".join(hist)
+
+
+@pytest.mark.parametrize("flags", [0, DYN])
+def test_relocated_slots_in_one_batch(engine, flags):
+    """Thirteen connections, each with the slot of a connection that has been open for a long time -- `total`
+    raised across 2^31, 2^32, 2^48 and 2^62 (tests/_takeover_far.py) --, one unrelocated and one fresh, two or
+    three messages each so the chain runs in registers across the boundary.  Payloads, records and slots are
+    the host twin's on the same slots (one_call), the device's bytes inflate with zlib and the history as its
+    dictionary, and every relocated connection ends as the unrelocated one, `total` apart."""
+    rng = far.rng_of(0x666172)
+    odd, edge, h_odd, h_edge = old_slots(rng)
+    cases = far.far_cases(far.DefSlot(odd).total, far.U_DEF)
+    edges = far.edge_cases(far.DefSlot(edge).total, far.U_DEF)
+    first = far.message(rng, h_odd, "text")
+    chain_odd = [first, far.message(rng, h_odd + first, "tiled", 5000), first[-300:]]
+    short = h_edge[-4000:-3983]
+    chain_edge = [short, b"", far.message(rng, h_edge + short, "runs")]
+    conns = [(odd, h_odd, s, chain_odd) for _, s in [("unrelocated", 0)] + cases]
+    conns += [(edge, h_edge, s, chain_edge) for _, s in [("unrelocated", 0)] + edges]
+    conns.append((bytes(CTX), b"", 0, chain_odd[:2]))                        # a fresh connection
+    # the other kinds of message cross 2^32 too, on further connections
+    below32 = dict(cases)["below 2^32"]
+    for kind in ("random", "period"):
+        conns.append((odd, h_odd, below32, [far.message(rng, h_odd, kind), far.message(rng, h_odd, "text", 300)]))
+    assert len(conns) == 15
+    slots = [far.DefSlot(s).relocated(shift) for s, _, shift, _ in conns]
+    msgs = [(c, m, B, 0) for c, (_, _, _, chain) in enumerate(conns) for m in chain]
+    want = one_call(engine, msgs, [EXT_S] * len(conns), slots, flags)       # the device == the host twin
+    at = 0
+    for c, (_, history, _, chain) in enumerate(conns):
+        stream = history
+        for m in chain:
+            d = zlib.decompressobj(-15, zdict=stream[-32768:]) if stream else zlib.decompressobj(-15)
+            assert d.decompress(want[at] + TAIL) == m, (c, len(m))
+            stream, at = stream + m, at + 1
+    for c in range(1, 1 + len(cases)):                                       # translation: connection 0 is unrelocated
+        far.assert_def_translated(slots[c], slots[0], conns[c][2], c)
+    e0 = 1 + len(cases)
+    for c in range(e0 + 1, e0 + 1 + len(edges)):
+        far.assert_def_translated(slots[c], slots[e0], conns[c][2], c)
+    per = len(chain_odd)
+    assert all(want[c * per:(c + 1) * per] == want[:per] for c in range(1, 1 + len(cases)))
+
+
+def test_closed_loop_at_a_far_position(engine):
+    """deflate on relocated slots -> encode -> decode -> message pass -> inflate on the matching relocated
+    inflate slots: the original messages, across 2^31 and across 2^32."""
+    import torch
+    from tests import _inflate_takeover as tk
+    from tests._helpers import gpu_decode
+    rng = far.rng_of(0x6C6F6F70)
+    dev = torch.device("cuda", engine.device)
+    odd, _, h_odd, _ = old_slots(rng)
+    cases = dict(far.far_cases(far.DefSlot(odd).total, far.U_DEF))
+    shifts = [cases["below 2^31"], cases["below 2^32"], cases["on 2^32"], cases["near 2^62"]]
+    n_conns = len(shifts)
+    ext = [EXT_S | gev_amd.EXT_CLIENT_TAKEOVER] * n_conns
+    d_ext = torch.tensor(ext, dtype=torch.uint8, device=dev)
+    slots = [far.DefSlot(odd).relocated(s) for s in shifts]
+    inf = tk.Slot()
+    inf.append(h_odd)
+    assert bytes(inf.ring) == far.DefSlot(odd).ring                          # the two windows hold the same stream
+    inf_slots = [inf.relocated(s) for s in shifts]
+    def_ctx = torch.from_numpy(slots_np(slots)).to(dev)
+    inf_ctx = tk.slots_to_device(inf_slots, dev)
+    state = torch.zeros((n_conns, 8), dtype=torch.uint8, device=dev)
+    first = far.message(rng, h_odd, "text")
+    chain = [first, far.message(rng, h_odd + first, "period", 5000), first[-300:]]
+    msgs = [(c, m, B, 0) for c in range(n_conns) for m in chain]
+    per, n = len(chain), len(msgs)
+    arena, src_bytes, rec, conn = build(msgs)
+    want, _ = model(msgs, ext, slots)
+    res = engine.deflate(rec, torch.from_numpy(arena).to(dev), src_bytes, msg_conn=conn, conn_ext=d_ext,
+                         contexts=def_ctx)
+    assert [res.payload(i) for i in range(n)] == want
+    wire_cap = sum(len(w) + 10 for w in want)
+    wire = torch.zeros(wire_cap + gev_amd._abi.OUT_PAD, dtype=torch.uint8, device=dev)
+    out_off = torch.zeros(n, dtype=torch.int64, device=dev)
+    esum = torch.zeros(64, dtype=torch.uint8, device=dev)
+    engine.encode_async(res.frames, n, res.out, wire, wire_cap, out_off, esum)
+    torch.cuda.synchronize(engine.device)
+    es = esum.cpu().numpy().view(gev_amd.SUMMARY_DTYPE)[0]
+    assert int(es["status"]) == gev_amd.OK
+    total = int(es["payload_bytes"])
+    offs = [int(x) for x in out_off.cpu().numpy()] + [total]
+    table = [(offs[c * per], offs[(c + 1) * per] - offs[c * per]) for c in range(n_conns)]
+    out = gpu_decode(engine, wire[:total].cpu().numpy(), np.array(table, np.int64))
+    assert int(out.summary_host()["frames"]) == n
+    m = engine.messages(out, state=state, conn_ext=d_ext)
+    assert m.messages_host().shape[0] == n
+    got = engine.inflate(out, m, 1 << 17, state=state, conn_ext=d_ext, contexts=inf_ctx)
+    s = got.summary_host()
+    assert int(s["frames"]) == n and int(s["errors"]) == 0
+    for i, (_, data, _, _) in enumerate(msgs):
+        assert got.message_bytes(i) == data, i
+    assert np.array_equal(def_ctx.cpu().numpy(), slots_np(slots))
+    after = inf_ctx.cpu().numpy()
+    assert np.array_equal(def_ctx.cpu().numpy()[:, 64:64 + 32768], after[:, 64:])
+    sent = sum(len(x) for x in chain)
+    for c, s in enumerate(shifts):
+        assert int.from_bytes(after[c, :8].tobytes(), "little") == 70001 + s + sent and not after[c, 8:64].any()
 
 
 def test_round_trip_on_the_device(engine):

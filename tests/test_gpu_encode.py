@@ -14,13 +14,14 @@ from tests._helpers import gpu_decode, host_result, pack_streams, random_stream
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(params=[0, 1, 2, 3, 4, 5],
-                ids=["auto", "one_tile", "two_tiles", "two_tiles_contiguous", "two_tiles_cyclic", "two_tiles_counter"])
+@pytest.fixture(params=[0, 1, 2, 3, 4, 5, 6],
+                ids=["auto", "one_tile", "two_tiles", "two_tiles_contiguous", "two_tiles_cyclic", "two_tiles_counter",
+                     "one_tile_cyclic"])
 def enc_variant(request, engine):
     """Every form of the encode kernel k_encode6 (GEVWS_TUNE_ENCODE_VARIANT):
     0 = the default (its step and run mode chosen per batch), 1 / 2 = one /
     two tiles a wave step, 3 / 4 / 5 = two tiles a step with contiguous /
-    cyclic / counter runs."""
+    cyclic / counter runs, 6 = one tile a step with cyclic runs."""
     try:
         engine.set_tuning(gev_amd._abi.TUNE_ENCODE_VARIANT, request.param)
     except RuntimeError:

@@ -453,3 +453,38 @@ def test_end_to_end_through_engine(engine):
             assert f.header.fin and f.header.rsv == 4 and f.header.opcode == 1
             assert zlib.decompressobj(-15).decompress(f.payload + b"\x00\x00\xff\xff") == text
             assert not carry.records_host().view(np.uint8).any() and carry.used == 0
+
+
+# ---------------------------------------------------------------------------- a carried message on an old connection
+def test_carried_message_on_relocated_slots(engine):
+    """A compressed message that began in an earlier pass, carried and inflated at its FIN, on the slots of
+    connections that have been open for a long time (tests/_takeover_far.py): `total` is raised so that the
+    carried message crosses 2^31, 2^32 and 2^62.  The device against the models, as everywhere here; the
+    payloads are zlib's with the history as its dictionary, so the expected bytes are the messages."""
+    from tests import _takeover_far as far
+    rng = far.rng_of(0x1CA0FA)
+    hist = far.history_messages(rng)
+    history = b"".join(hist[:3])
+    base = it.Slot()
+    base.append(history)
+    cases = dict(far.far_cases(base.total, far.U_INF))
+    shifts = [0, cases["below 2^31"], cases["below 2^32"], cases["on 2^32"], cases["near 2^62"]]
+    slots = [base.relocated(s) for s in shifts]
+    one = history[-900:-200]
+    two = far.message(rng, history + one, "text")
+    three = two[-300:]
+    ch = far.peer_chain(history, [one, two, three])
+    assert it.empty_window_differs(ch[1], two) and it.empty_window_differs(ch[2], three)
+    cuts = (1, 1025, len(ch[1]) // 2, len(ch[1]) - 1, 17)
+    passes = [[[(1, RSV1, B, ch[0]), (0, RSV1, B, ch[1][:k])] for k in cuts],
+              [[(1, 0, C, ch[1][k:]), (1, RSV1, B, ch[2])] for k in cuts]]
+    res, ctx = icm.chain_device(engine, passes, np.full(len(shifts), TAKE, np.uint8), BIG, BIG, slots=slots,
+                                tag="carried, relocated")
+    dev = it.slots_from_device(ctx)
+    assert dev == [s.image() for s in slots]
+    assert icm.sequences(len(shifts), [g for _, g, _ in res]) == [[(B, one), (B, two), (B, three)]] * len(shifts)
+    near = it.Slot(dev[0])
+    for c, s in enumerate(shifts):
+        far_slot = it.Slot(dev[c])
+        assert (far_slot.total, far_slot.broken, far_slot.ring) == (near.total + s, 0, near.ring), c
+    assert near.total == 70001 + len(one) + len(two) + len(three)

@@ -22,6 +22,7 @@ from tests import _inflate_gpu_model as gm
 from tests import _inflate_model as im
 from tests import _inflate_takeover as tk
 from tests import _messages_model as mm
+from tests import _takeover_far as far
 
 pytestmark = pytest.mark.gpu
 
@@ -502,3 +503,75 @@ def test_a_conn_index_past_n_conns_is_invalid_and_writes_nothing(engine):
     assert (int(s["frames"]), int(s["payload_bytes"]), int(s["payload_len"])) == (0, 0, 0)
     assert np.all(res["out"] == 0xEE) and np.all(res["inflated"].view(np.uint8) == 0xEE)
     assert bool((ctx == before).all()) and bool((got["dev"]["state"] == state_before).all())
+
+
+# ---------------------------------------------------------------------------- 9. old connections: relocated slots
+def old_slots(rng):
+    """(the `odd` slot at 70 001 bytes, the `edge` slot at 131 055, their histories): tests/_takeover_far.py."""
+    hist = far.history_messages(rng)
+    odd, edge = tk.Slot(), tk.Slot()
+    odd.append(b"".join(hist[:3]))
+    edge.append(b"".join(hist))
+    return odd, edge, b"".join(hist[:3]), b"".join(hist)
+
+
+def relocated_batch():
+    """(plan, conns, slots, number of far cases, number of edge cases) of the test below."""
+    rng = far.rng_of(0x666172)
+    odd, edge, h_odd, h_edge = old_slots(rng)
+    cases = far.far_cases(odd.total, far.U_INF)
+    edges = far.edge_cases(edge.total, far.U_INF)
+    first = far.message(rng, h_odd, "text")
+    chain_odd = [first, far.message(rng, h_odd + first, "tiled", 5000), first[-300:]]
+    short = h_edge[-4000:-3983]
+    chain_edge = [short, b"", far.message(rng, h_edge + short, "runs")]
+    plan = [(odd, h_odd, s, chain_odd, 6) for _, s in [("unrelocated", 0)] + cases]
+    plan += [(edge, h_edge, s, chain_edge, 9) for _, s in [("unrelocated", 0)] + edges]
+    plan.append((tk.Slot(), b"", 0, chain_odd[:2], 6))                        # a fresh connection
+    below32 = dict(cases)["below 2^32"]
+    for kind in ("random", "period"):                                         # the other kinds cross 2^32 too
+        plan.append((odd, h_odd, below32, [far.message(rng, h_odd, kind), first[:300]], 1))
+    assert len(plan) == 15
+    conns, slots = [], []
+    for slot, history, shift, chain, level in plan:
+        conn = Conn(TAKE)
+        for p, m in zip(far.peer_chain(history, chain, level), chain):
+            conn.add(frames_of(p, B, [len(p) // 3] if len(p) > 3000 else []), p, m)
+        if history:                                                           # ... and the farthest distance there is
+            whole = history + b"".join(chain)
+            conn.add(frames_of(tk.match_at(32768), B), tk.match_at(32768), whole[-32768:][:3])
+            assert tk.empty_window_differs(conn.msgs[0][1], chain[0])
+        conns.append(conn)
+        slots.append(slot.relocated(shift))
+    return plan, conns, slots, len(cases), len(edges)
+
+
+def test_relocated_slots_in_one_batch(engine):
+    """Fifteen connections, each with the slot of a connection that has been open for a long time -- `total`
+    raised across 2^31, 2^32, 2^48 and 2^62 --, one unrelocated and one fresh, three or four messages each so
+    the chain runs in registers across the boundary.  The payloads are zlib's, made with the history as its
+    dictionary, so the expected bytes are the messages; records, bytes and slots are the model's (run_pass)
+    and the host twin's on the same relocated slots, and every relocated connection ends as the unrelocated
+    one, `total` apart."""
+    plan, conns, slots, n_far, n_edge = relocated_batch()
+    before = [s.image() for s in slots]
+    ext = [TAKE] * len(conns)
+    ctx = device_slots(engine, slots, ext)
+    ginf, winf = run_pass(engine, [c.frames() for c in conns], ext, ctx, slots, limit=1 << 17, tag="relocated")
+    assert winf["errors"] == 0
+    per = message_bytes(ginf, winf)
+    dev = tk.slots_from_device(ctx)
+    for c, conn in enumerate(conns):
+        assert per[c] == [(im.OK, d) for d in expected_data(conn)], c         # zlib's reference: the messages
+        host = bytearray(before[c])                                           # the host twin on the same slot
+        for _, p, d in conn.msgs:
+            assert gev_amd.inflate_raw_ctx(p, 1 << 17, host) == (im.OK, d), c
+        assert dev[c] == bytes(host), c
+
+    def translated(c, base):
+        a, b = tk.Slot(dev[c]), tk.Slot(dev[base])
+        assert (a.total, a.broken, a.ring) == (b.total + plan[c][2], 0, b.ring), c
+    for c in range(1, 1 + n_far):
+        translated(c, 0)
+    for c in range(2 + n_far, 2 + n_far + n_edge):
+        translated(c, 1 + n_far)

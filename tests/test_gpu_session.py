@@ -116,6 +116,66 @@ def check_echo_session(engine, echo_runs, passes, F, deflate_flags=0):
         assert seen == s.predicted_carries(conns, run.cuts, passes)
 
 
+LEAD_BYTES = (1 << 32) + 4096
+
+
+@pytest.mark.parametrize("F", (None, 1000), ids=["None", "1000"])
+def test_echo_session_behind_a_payload_arena_past_4gib(engine, echo_runs, F):
+    """The one-pass echo session once more with every payload offset, body
+    offset and aux offset above 2^32: a leading connection holds one frame of
+    2^32 + 4096 payload bytes with a reserved opcode (s.run_far_session), the
+    320 connections follow it.  Whatever an offset cut to 32 bits would read
+    is the 0xA5 fill of the frame's first MiB."""
+    import torch
+    free, _ = torch.cuda.mem_get_info(engine.device)
+    if free < 12 << 30:
+        pytest.skip(f"the far arena needs about 9 GiB of device memory, {free / 2**30:.1f} GiB are free")
+    conns = s.echo_conns()
+    n = len(conns)
+    run = s.run_far_session(engine, conns, LEAD_BYTES, F)
+    print("far session: %.2f s" % run.seconds)
+    # the offsets really are far: the decode's arena, every record behind the leading frame, the aux region
+    lead16 = (LEAD_BYTES + 15) // 16 * 16
+    assert int(run.decode_summary["payload_bytes"]) > 1 << 32
+    assert int(run.first_frame[1]) == 1 and int(run.payload_off[0]) == 0
+    assert int(run.payload_off[1:].min()) == lead16 >= 1 << 32
+    assert run.aux_off >= 1 << 32
+    # the client's view: every connection is sent what the checker expects
+    tally, checked = Counter(), 0
+    for c, conn in enumerate(conns):
+        try:
+            s.check_echo_conn(conn, run.sent[c + 1], F, tally)
+        except s.CheckError as e:
+            raise AssertionError("connection %d (%s, ext %d): %s" % (c, conn.heavy or "light", conn.ext, e)) from None
+        checked += 1
+    assert checked == n == 320                                # the share left out is 0
+    assert all(tally[k] > 0 for k in s.REPLY_KINDS), tally
+    assert tally["needs the window"] > 0
+    assert run.gathered == run.sent                           # the gather is the plan's entries
+    # the leading connection: a reserved opcode is a protocol error
+    assert run.sent[0] == bytes.fromhex("880203ea")
+    assert int(run.conn_flags[0]) & (gev_amd.CTL_SHUTDOWN | gev_amd.CTL_FAILED) == gev_amd.CTL_SHUTDOWN | gev_amd.CTL_FAILED
+    for c, conn in enumerate(conns):
+        assert bool(int(run.conn_flags[c + 1]) & gev_amd.CTL_SHUTDOWN) == (conn.dead_at is not None), c
+    # without a limit the bytes do not depend on the arena's layout: the same session without the leading frame
+    if F is None:
+        base = echo_run(engine, echo_runs, 1, None)
+        for c in range(n):
+            assert run.sent[c + 1] == base.wire(c), (c, conns[c].heavy)
+    # the join without GEVWS_JOIN_ALL leaves single-frame plain bodies in the far arena: the same bytes there
+    b0, b1 = run.bodies_in_place, run.bodies_copied
+    whole = b1["flags"] & gev_amd.BODY_WHOLE != 0
+    assert np.array_equal(b0["flags"] & gev_amd.BODY_WHOLE != 0, whole) and whole.sum() > 300
+    assert np.array_equal(b0["length"], b1["length"]) and np.array_equal(b0["conn"], b1["conn"])
+    placed = whole & (b0["flags"] & (gev_amd.BODY_JOINED | gev_amd.BODY_INFLATED) == 0)
+    assert placed.sum() > 50 and int(b0["off"][placed & (b0["length"] > 0)].min()) >= 1 << 32
+    assert np.all(b1["flags"][whole] & (gev_amd.BODY_JOINED | gev_amd.BODY_INFLATED) != 0)
+    assert all(a == b for a, b in run.body_bytes)
+    assert sum(len(a) for a, _ in run.body_bytes) > 50000
+    del run
+    torch.cuda.empty_cache()
+
+
 def test_echo_session_cuts_everywhere(engine, echo_runs):
     """Over the cuttings that ran, a pass boundary fell in every place a frame has."""
     classes = Counter()

@@ -20,6 +20,7 @@ from tests import _inflate_corpus as ic
 from tests import _inflate_gpu_model as gm
 from tests import _inflate_model as im
 from tests import _inflate_takeover as tk
+from tests import _takeover_far as far
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAN = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fno-sanitize-recover=all", "-g", "-O1"]
@@ -192,6 +193,135 @@ def test_slot_is_a_function_of_the_stream_not_of_the_calls():
         model = tk.Slot()
         model.append(words[:at])
         assert bytes(ctx) == model.image(), cuts
+
+
+# ---------------------------------------------------------------------------- old connections: relocated slots
+# A connection that has inflated 2 GiB, 4 GiB or far more: tests/_takeover_far.py.  Two references, neither of
+# them the relocated run: zlib, which made the payload with the history as its dictionary (the output must be
+# the message), and the same call on the unrelocated slot.
+@pytest.fixture(scope="module")
+def old():
+    """The old slots -- `odd` at 70 001 bytes, `edge` at 131 055 -- and their plain history."""
+    rng = far.rng_of(0x6F6C64)
+    hist = far.history_messages(rng)
+    ctx, slots = fresh(), {}
+    for k, (p, m) in enumerate(zip(tk.chain(hist, 6), hist)):
+        assert gev_amd.inflate_raw_ctx(p, BIG, ctx) == (im.OK, m)
+        if k == 2:
+            slots["odd"] = bytes(ctx)
+    slots["edge"] = bytes(ctx)
+    model = tk.Slot()
+    model.append(b"".join(hist))
+    assert slots["edge"] == model.image() and tk.Slot(slots["odd"]).total == 70001 and model.total == 131055
+    return dict(slots=slots, hist={"odd": b"".join(hist[:3]), "edge": b"".join(hist)})
+
+
+peer_chain = far.peer_chain
+
+
+def assert_inf_translated(ctx, near: bytes, shift: int, tag=""):
+    """The slot is the unrelocated run's with `total` larger by exactly `shift`: the same ring image, the
+    same `broken` byte, zeros elsewhere in the head (tk.Slot asserts those)."""
+    a, b = tk.Slot(bytes(ctx)), tk.Slot(near)
+    assert a.total == b.total + shift, (tag, a.total, b.total, shift)
+    assert a.broken == b.broken and a.ring == b.ring, tag
+
+
+def run_far_chain(slot0: bytes, payloads, shift: int, caps, near=None, tag=""):
+    """The payloads one after the other on slot0 relocated by `shift`, against the unrelocated run
+    [((status, bytes), slot after)], which is returned for the next shift to share."""
+    if near is None:
+        ctx, near = bytearray(slot0), []
+        for p, cap in zip(payloads, caps):
+            got = gev_amd.inflate_raw_ctx(p, cap, ctx)
+            near.append((got, bytes(ctx)))
+    ctx = bytearray(tk.Slot(slot0).relocated(shift).image())
+    for k, (p, cap, (want, slot_near)) in enumerate(zip(payloads, caps, near)):
+        got = gev_amd.inflate_raw_ctx(p, cap, ctx)
+        assert got[0] == want[0] and len(got[1]) == len(want[1]) and got[1] == want[1], (tag, k, got[0], want[0])
+        assert_inf_translated(ctx, slot_near, shift, (tag, k))
+    return near
+
+
+def test_relocated_slots_cross_every_boundary(old):
+    rng = far.rng_of(0x666172)
+    slot0, history = old["slots"]["odd"], old["hist"]["odd"]
+    cases = far.far_cases(tk.Slot(slot0).total, far.U_INF)
+    combos = [(6, zlib.Z_DEFAULT_STRATEGY), (1, zlib.Z_FIXED), (9, zlib.Z_DEFAULT_STRATEGY), (6, zlib.Z_DEFAULT_STRATEGY),
+              (1, zlib.Z_DEFAULT_STRATEGY)]
+    for kind, (level, strategy) in zip(far.KINDS, combos):
+        # three messages: the second and third run on a slot the code itself wrote at the far position
+        first = far.message(rng, history, kind)
+        msgs = [first, far.message(rng, history + first, far.KINDS[(far.KINDS.index(kind) + 1) % 5], 5000),
+                first[-300:]]
+        payloads = peer_chain(history, msgs, level, strategy)
+        assert tk.empty_window_differs(payloads[0], msgs[0]) and tk.empty_window_differs(payloads[2], msgs[2])
+        near = None
+        for name, shift in cases:
+            near = run_far_chain(slot0, payloads, shift, [BIG] * 3, near, (name, kind))
+        assert [g for g, _ in near] == [(im.OK, m) for m in msgs], kind      # zlib's dictionary run: the messages
+
+
+def test_short_and_empty_messages_right_at_a_boundary(old):
+    rng = far.rng_of(0x65646765)
+    slot0, history = old["slots"]["edge"], old["hist"]["edge"]
+    short = history[-4000:-3983]
+    msgs = [short, b"", far.message(rng, history + short, "text"), b"", far.message(rng, history, "runs", 17)]
+    payloads = peer_chain(history, msgs)
+    assert len(short) == 17 and payloads[1] == b"\x00" and tk.empty_window_differs(payloads[0], short)
+    near = None
+    for name, shift in far.edge_cases(tk.Slot(slot0).total, far.U_INF):
+        near = run_far_chain(slot0, payloads, shift, [BIG] * 5, near, name)
+    assert [g for g, _ in near] == [(im.OK, m) for m in msgs]
+
+
+def test_distances_on_relocated_slots(old):
+    """An old slot holds 32 768 bytes of history wherever it stands, so every distance up to 32 768 is
+    allowed -- also where the low 32 bits of `total` alone would say 4 465 bytes.  history + 1 is out of
+    reach only on a young slot (32 769 is no DEFLATE distance), and stays GEVWS_MSG_ERR_DEFLATE there."""
+    assert tk.match_at(32768) == tk.match3_at_32768()
+    slot0, history = old["slots"]["odd"], old["hist"]["odd"]
+    window = history[-tk.WIN:]
+    cases = far.far_cases(tk.Slot(slot0).total, far.U_INF)
+    on32 = tk.Slot(slot0).relocated(dict(cases)["on 2^32"])
+    young_len = on32.total & 0xFFFFFFFF
+    assert young_len == 4465
+    for dist in (32768, young_len + 1, young_len, 1):
+        want = (window[-dist:] * 3)[:3]
+        assert tk.zlib_inflate_dict(window, tk.match_at(dist)) == (False, want)
+        near = None
+        for name, shift in cases:
+            near = run_far_chain(slot0, [tk.match_at(dist)], shift, [BIG], near, (name, dist))
+        assert near[0][0] == (im.OK, want), dist
+    young = fresh()
+    h = history[:young_len]
+    assert gev_amd.inflate_raw_ctx(ic.deflate(h, 0), BIG, young) == (im.OK, h)
+    assert gev_amd.inflate_raw_ctx(tk.match_at(young_len), BIG, bytearray(young)) == (im.OK, h[:3])
+    assert gev_amd.inflate_raw_ctx(tk.match_at(young_len + 1), BIG, young) == (im.ERR_DEFLATE, b"")
+    assert tk.zlib_inflate_dict(h, tk.match_at(young_len + 1))[0]
+
+
+def test_relocated_failures(old):
+    """A failure at a far position loses the context as it does near zero, and a relocated slot that is
+    broken stays lost."""
+    rng = far.rng_of(0x62726B)
+    slot0, history = old["slots"]["odd"], old["hist"]["odd"]
+    m = far.message(rng, history, "text")
+    p, = peer_chain(history, [m])
+    cases = far.far_cases(tk.Slot(slot0).total, far.U_INF)
+    for bad, cap, status in ((b"\x06garbage", BIG, im.ERR_DEFLATE), (p, 70000, im.ERR_TOO_BIG)):
+        near = None
+        for name, shift in cases:
+            near = run_far_chain(slot0, [bad, p, ic.deflate(b"on its own")], shift, [cap, BIG, BIG], near, (name, status))
+        assert [g[0] for g, _ in near] == [status] * 3 and near[1][0][1] == near[2][0][1] == b""
+        assert tk.Slot(near[2][1]).broken == status and tk.Slot(near[2][1]).total == 70001
+        if status == im.ERR_TOO_BIG:
+            assert near[0][0][1] == m[:70000]                                # the bytes up to the limit
+        broken = near[0][1]                                                  # a broken slot, then relocated
+        for name, shift in cases:
+            ctx = bytearray(tk.Slot(broken).relocated(shift).image())
+            before = bytes(ctx)
+            assert gev_amd.inflate_raw_ctx(p, BIG, ctx) == (status, b"") and bytes(ctx) == before, name
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
