@@ -35,6 +35,7 @@ from ._abi import HANDLER_ECHO_BINARY, HANDLER_ECHO_TEXT, HANDLER_NONE
 from ._abi import (CONTROL_NO_PING_FOR_PONG, CTL_FAILED, CTL_SHUTDOWN, MSG_ERR_CLOSED, WIRE_CONTROL, WIRE_DEFLATED,
                    WIRE_PLAIN)
 from ._abi import ROOM_NONE, ROOMS_SKIP_SENDER
+from ._abi import CHANGE_NONE, CHANGE_REJECTED, MSG_COMMAND
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
                    SUMMARY_UNORDERED, TILE, Header)
@@ -240,6 +241,19 @@ def fragment_records(records: np.ndarray, max_fragment_bytes: int,
     frags = call(int(max_frags))
     s = summary[0]
     return frags[: int(s["frames"]) if int(s["status"]) == OK else 0], first, s
+
+
+def room_command_parse(body: bytes, n_rooms: int) -> Tuple[int, int]:
+    """gevws_room_command_parse: what gevws_room_commands_async makes of a
+    delivered text message of these bytes -> (class, room): class 0 no
+    command, 1 a change ("/join N" with N < n_rooms: room N; "/leave": room
+    ROOM_NONE), 2 a rejected join; room is ROOM_NONE unless the class is 1."""
+    body = bytes(body)
+    room = ctypes.c_uint32(0)
+    st = lib.gevws_room_command_parse(ctypes.c_char_p(body), len(body), int(n_rooms), ctypes.byref(room))
+    if st < 0:
+        raise RuntimeError(f"gevws_room_command_parse: {status_string(st)}")
+    return st, int(room.value)
 
 
 def _torch():
@@ -470,6 +484,8 @@ class Responses:
     # from Engine.broadcast: message m's index in the plain list / the deflate list or -1 (echo.reply_of: the plain one)
     plain_of: Optional[np.ndarray] = None
     def_of: Optional[np.ndarray] = None
+    # from Engine.broadcast(commands=True): the pass's room commands, for Rooms.update(changes=...)
+    room_changes: Optional["RoomChanges"] = None
 
     def summary_host(self) -> np.ndarray:
         return self.summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
@@ -497,6 +513,33 @@ class Responses:
         first, count = int(cs["first"]), int(cs["count"])
         return b"".join(wires[int(e["wire"])][int(e["off"]): int(e["off"]) + int(e["len"])].tobytes()
                         for e in send[first: first + count])
+
+
+@dataclass
+class RoomChanges:
+    """What gevws_room_commands_async made of a pass's bodies, on the device:
+    the {conn, room} change records in message order, change_of[m] = message
+    m's change, CHANGE_NONE or CHANGE_REJECTED, and the step's summary (frames
+    = the changes).  Rooms.update(changes=...) hands the records, their
+    capacity and the summary to gevws_rooms_update_async, so neither the
+    records nor their count visit the host."""
+    changes: "object"        # uint8 [max_changes, 8] (gevws_room_change records)
+    change_of: "object"      # int64 [max(n_messages, 1)]
+    summary: "object"        # uint8 [64] (gevws_summary)
+    max_changes: int
+    n_messages: int
+
+    def summary_host(self) -> np.ndarray:
+        return self.summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
+
+    def host(self) -> np.ndarray:
+        """The change records written (ROOM_CHANGE_DTYPE); none unless the step's status is OK."""
+        s = self.summary_host()
+        n = min(int(s["frames"]), self.max_changes) if int(s["status"]) == OK else 0
+        return self.changes[:n].cpu().numpy().reshape(-1).view(ROOM_CHANGE_DTYPE)
+
+    def change_of_host(self) -> np.ndarray:
+        return self.change_of[: self.n_messages].cpu().numpy()
 
 
 @dataclass
@@ -550,9 +593,11 @@ class Rooms:
         torch = _torch()
         dev = torch.device("cuda", engine.device)
         n_conns = int(conn_room.numel())
-        d_changes, n_changes = None, 0
+        d_changes, n_changes, prev = None, 0, None
         if changes is not None:
-            if isinstance(changes, torch.Tensor):   # gevws_room_change records in device memory
+            if isinstance(changes, RoomChanges):   # the room-command step's: the count stays on the device
+                d_changes, n_changes, prev = changes.changes, changes.max_changes, changes.summary
+            elif isinstance(changes, torch.Tensor):   # gevws_room_change records in device memory
                 nbytes = changes.numel() * changes.element_size()
                 if nbytes % 8 or not changes.is_contiguous():
                     raise ValueError(f"{what}: changes: a contiguous tensor of 8-byte {{conn, room}} records")
@@ -578,7 +623,7 @@ class Rooms:
         first = torch.empty(n_rooms + 1, dtype=torch.int32, device=dev)
         members = torch.empty(max(n_conns, 1), dtype=torch.int32, device=dev)
         summary = torch.zeros(64, dtype=torch.uint8, device=dev)
-        engine.rooms_update_async(conn_room if n_conns else None, n_conns, n_rooms, d_changes, n_changes, None,
+        engine.rooms_update_async(conn_room if n_conns else None, n_conns, n_rooms, d_changes, n_changes, prev,
                                   conn_send, plan_summary, 0, out, first, members, summary, stream)
         torch.cuda.synchronize(engine.device)
         s = summary.cpu().numpy().view(SUMMARY_DTYPE)[0]
@@ -606,7 +651,9 @@ class Rooms:
         (gevws_rooms_update_async); this object stays valid.  changes: {conn,
         room} records applied in order, the last one of a connection wins, room
         ROOM_NONE leaves -- a ROOM_CHANGE_DTYPE array or an (n, 2) integer array
-        (uploaded), or a device tensor of such records.  closed: the pass's
+        (uploaded), a device tensor of such records, or the RoomChanges of
+        Engine.broadcast(commands=True) (its summary gates the call and gives
+        the count on the device).  closed: the pass's
         Responses; every connection it shut down (CTL_SHUTDOWN in its device
         conn_send) leaves its room, whatever `changes` says.  n_rooms: a larger room space (None: unchanged)."""
         return self._updated(engine, self.conn_room, self.n_rooms if n_rooms is None else int(n_rooms), changes,
@@ -1601,9 +1648,24 @@ class Engine:
         if st != OK:
             raise RuntimeError(f"gevws_rooms_update_async: {status_string(st)}")
 
+    def room_commands_async(self, bodies, max_messages: int, msg_summary, join_summary, ctl_summary, out,
+                            src_bytes: int, n_conns: int, n_rooms: int, flags: int, changes, max_changes: int,
+                            change_of, summary, stream=None) -> None:
+        """gevws_room_commands_async on device tensors: "/join N" and "/leave"
+        in delivered text bodies become {conn, room} records in `changes`, and
+        those bodies are stripped in place (status MSG_COMMAND)."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        st = lib.gevws_room_commands_async(
+            self._ctx, _stream_handle(stream), ptr(bodies), max_messages, ptr(msg_summary), ptr(join_summary),
+            ptr(ctl_summary), ptr(out), src_bytes, n_conns, n_rooms, flags, ptr(changes), max_changes,
+            ptr(change_of), ptr(summary))
+        if st != OK:
+            raise RuntimeError(f"gevws_room_commands_async: {status_string(st)}")
+
     def broadcast(self, out: "Batch", msgs: "Messages", bodies: "Bodies", policy: int, conn_ext, rooms: "Rooms",
                   window_bits=None, flags: int = 0, rooms_flags: int = 0, control_flags: int = 0,
-                  gather: bool = False, stream=None, max_fragment_bytes: Optional[int] = None) -> "Responses":
+                  gather: bool = False, stream=None, max_fragment_bytes: Optional[int] = None,
+                  commands: bool = False) -> "Responses":
         """Everything a pass sends when a message goes to its sender's room:
         control -> reply_rooms -> deflate -> the three encodes -> room plan ->
         (gather).  The arguments are respond's, without contexts (a broadcast
@@ -1612,7 +1674,10 @@ class Engine:
         step's.  The result is respond's: conn_bytes(c) and host_sends() work
         unchanged; echo.def_conn / echo.plain_conn name the senders.
         max_fragment_bytes: one frame size limit for every recipient (a
-        message is framed once)."""
+        message is framed once).  commands=True puts the room-command step
+        between the control step and the reply step: "/join N" and "/leave"
+        messages leave the broadcast and come back as room_changes, for
+        Rooms.update(changes=res.room_changes, closed=res) behind the pass."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         n_conns, nf, nm = out.n_conns, msgs.n_frames, bodies.n_messages
@@ -1631,6 +1696,16 @@ class Engine:
         self.control_async(out.frames, nf, out.conn_out, n_conns, out.summary, out.payload, aux_off, aux_cap,
                            msgs.msg_of, msgs.messages, nm, msgs.conn_msg, msgs.summary, bodies.bodies, bodies.summary,
                            control_flags, ctl, ctl_conn, ctl_of, msg_end, conn_ctl, ctl_sum, stream)
+        room_changes = None
+        if commands:
+            room_changes = RoomChanges(changes=z(capm, 8), change_of=torch.full((capm,), -1, dtype=torch.int64,
+                                                                                device=dev),
+                                       summary=z(64), max_changes=nm, n_messages=nm)
+            if nm:
+                self.room_commands_async(bodies.bodies, nm, msgs.summary, bodies.summary, ctl_sum, bodies.out,
+                                         int(bodies.summary_host()["payload_bytes"]), n_conns, rooms.n_rooms, 0,
+                                         room_changes.changes, nm, room_changes.change_of, room_changes.summary,
+                                         stream)
         def_msgs, def_conn, def_sum = z(capm, 24), z(capm, dt=torch.int32), z(64)
         plain, plain_conn, plain_sum = z(capm, 32), z(capm, dt=torch.int32), z(64)
         plain_of = torch.full((capm,), -1, dtype=torch.int64, device=dev)
@@ -1642,6 +1717,9 @@ class Engine:
         cs, ds, ps = host(ctl_sum), host(def_sum), host(plain_sum)
         if int(cs["status"]) != OK:
             raise RuntimeError(f"broadcast: control: {status_string(int(cs['status']))} ({int(cs['errors'])})")
+        if room_changes is not None and int(room_changes.summary_host()["status"]) != OK:
+            rs = room_changes.summary_host()
+            raise RuntimeError(f"broadcast: room_commands: {status_string(int(rs['status']))} ({int(rs['errors'])})")
         if int(ds["status"]) != OK or int(ps["status"]) != OK:
             raise RuntimeError(f"broadcast: reply_rooms: {status_string(int(ds['status']))} ({int(ds['errors'])} records)")
         nd, npl, nr = int(ds["frames"]), int(ps["frames"]), int(cs["frames"])
@@ -1710,7 +1788,7 @@ class Engine:
                          conn_ctl=conn_ctl[:n_conns].cpu().numpy().reshape(-1).view(CONN_CTL_DTYPE), ctl_summary=cs,
                          send=send, conn_send=conn_send, summary=plan_sum, n_conns=n_conns, send_buf=send_buf,
                          conn_buf=conn_buf, gather_summary=gsum, plain_of=plain_of[:nm].cpu().numpy(),
-                         def_of=def_of[:nm].cpu().numpy())
+                         def_of=def_of[:nm].cpu().numpy(), room_changes=room_changes)
 
     def messages(self, out: "Batch", state=None, max_messages: Optional[int] = None, stream=None, *,
                  conn_ext=None) -> "Messages":
@@ -2354,4 +2432,4 @@ __all__ = ["Engine", "Batch", "Comm", "RingBuffer", "Connection", "Protocol", "H
            "deflate_raw_ctx", "deflate_negotiate_takeover", "DEF_CTX_BYTES", "EXT_SERVER_TAKEOVER",
            "NEGOTIATE_SERVER_TAKEOVER", "Carry", "CARRY_DTYPE", "CARRY_OPEN", "CARRY_LOST",
            "CARRY_COMPRESSED", "CARRY_KEEP_COMPRESSED", "Rooms", "ROOM_NONE", "ROOMS_SKIP_SENDER",
-           "ROOM_CHANGE_DTYPE"]
+           "ROOM_CHANGE_DTYPE", "RoomChanges", "room_command_parse", "MSG_COMMAND", "CHANGE_NONE", "CHANGE_REJECTED"]

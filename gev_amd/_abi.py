@@ -97,6 +97,9 @@ WIRE_PLAIN, WIRE_DEFLATED, WIRE_CONTROL = 0, 1, 2  # gevws_send.wire
 # rooms (gevws_reply_rooms_async, gevws_room_plan_async)
 ROOM_NONE = 0xFFFFFFFF  # d_conn_room: the connection is in no room
 ROOMS_SKIP_SENDER = 1  # call flag of both: a sender is not sent its own messages
+# room commands (gevws_room_commands_async)
+MSG_COMMAND = 10  # gevws_body.status of a stripped "/join N" or "/leave" message
+CHANGE_NONE, CHANGE_REJECTED = -1, -2  # d_change_of: no command, a join whose room is not < n_rooms
 
 IN_PAD = 64
 MEM_DEFAULT, MEM_FINE, MEM_UNCACHED = 0, 1, 2  # gevws_device_alloc kinds
@@ -382,6 +385,11 @@ SIGNATURES = {
                                              P, P]),
     "gevws_rooms_update_async": (ctypes.c_int, [P, P, P, ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_uint64, P, P,
                                                 P, ctypes.c_uint32, P, P, P, P]),
+    "gevws_room_commands_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, P, P, ctypes.c_uint64,
+                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_uint64,
+                                                 P, P]),
+    "gevws_room_command_parse": (ctypes.c_int, [P, ctypes.c_uint64, ctypes.c_uint32,
+                                                ctypes.POINTER(ctypes.c_uint32)]),
     "gevws_fragment_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, ctypes.c_uint32, P,
                                             ctypes.c_uint64, P, P]),
     "gevws_fragment_offsets_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, P, P, P, P]),

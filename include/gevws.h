@@ -1630,6 +1630,101 @@ int gevws_rooms_update_async(gevws_ctx *ctx, void *stream, const uint32_t *d_con
                              uint32_t *d_conn_room_out, uint32_t *d_room_first_out, uint32_t *d_room_members_out,
                              gevws_summary *d_summary);
 
+/* Room commands: a client enters and leaves a room by what it sends.  "/join N"
+ * and "/leave" in delivered text messages become the change records of
+ * gevws_rooms_update_async on the device, and leave the broadcast (the
+ * reference has no rooms and no commands).  Additions to ABI version 3:
+ * nothing above changes.  The step stands behind the control step and in front
+ * of the room reply step:
+ *   ... -> join -> control -> gevws_room_commands_async ->
+ *   gevws_reply_rooms_async -> ... -> gevws_room_plan_async -> gather, and
+ *   between two passes gevws_rooms_update_async with d_changes / max_changes of
+ *   this call and its d_summary as d_prev.
+ * The message pass, the inflate step and the join run first, so a command that
+ * arrives fragmented, split over two passes or compressed is a command like
+ * any other by the time this step looks at it.
+ *
+ * The rule (gev_amd/csrc/gevws_room_command.hpp; gevws_room_command_parse is
+ * the same rule on host bytes).
+ *   - Looked at.  A body is looked at exactly when it is delivered
+ *     (GEVWS_BODY_WHOLE), its opcode is 1 and its length is 6..16.  Only its
+ *     first `length` bytes count, whatever lies behind them.
+ *   - Leave.  The 6 bytes "/leave": the change {conn, GEVWS_ROOM_NONE}.
+ *   - Join.  The 6 bytes "/join " followed by 1..10 bytes that are all '0'..'9'
+ *     and nothing else; leading zeros are allowed; the value is taken in 64
+ *     bits.  A value < n_rooms: the change {conn, value} (a join, or a move for
+ *     a connection that has a room).  Any other value: a rejected command,
+ *     which is stripped and makes no change.  4294967295 never passes:
+ *     GEVWS_ROOM_NONE is not < n_rooms.
+ *   - Everything else -- "/join" without digits, "/join 3\n", "/JOIN 3",
+ *     "/leave ", a binary message of the same bytes -- is no command and is
+ *     broadcast as before.
+ *
+ * gevws_room_commands_async
+ *   - Inputs.  d_bodies / max_messages / d_msg_summary: the bodies are the first
+ *     min(d_msg_summary->frames, max_messages).  d_join_summary the join's,
+ *     d_ctl_summary the control step's (may be NULL), d_out / src_bytes the
+ *     join's d_out and its readable bytes (what the deflate step is given).
+ *     d_out starts on a 16-byte boundary, and a looked-at body is read as the
+ *     whole aligned 16-byte vector at its `off`, as the join reads d_payload: the
+ *     vector that holds the last byte of d_out is readable.  n_conns, n_rooms:
+ *     the room tables'.  flags: none is defined.
+ *   - d_changes (max_changes records): the changes in message order, that is by
+ *     connection and then in stream order, so the update's rule that the last
+ *     change of a connection wins is the client's last command.
+ *   - d_change_of (max_messages entries): for each of the bodies the index of
+ *     its change, -1 for no command, -2 for a rejected command.
+ *   - Strip.  Every command body, accepted or rejected, is stripped in place as
+ *     the control step strips a body behind a cut: off = length = flags = 0 and
+ *     status GEVWS_MSG_COMMAND; conn and opcode stay.  No other body changes by
+ *     a byte, and no byte of d_out is written.
+ *   - d_summary: frames = changes written, payload_len = bodies stripped,
+ *     payload_bytes = rejected commands, errors = 0, status GEVWS_OK.
+ *   - Capacity.  More changes than max_changes is GEVWS_ERR_CAPACITY: frames
+ *     holds the need, the other fields are zero and nothing else is written --
+ *     d_bodies stays byte for byte, so the caller retries.
+ *   - Gates.  A failed d_msg_summary, d_join_summary or (given) d_ctl_summary,
+ *     no messages, or max_messages == 0 give a zero summary; nothing else is
+ *     read or written.
+ *   - Malformed input.  A delivered body with neither GEVWS_BODY_JOINED nor
+ *     GEVWS_BODY_INFLATED or with conn >= n_conns (the reply step's two, on the
+ *     same bodies), and a looked-at body with off % 16 != 0 or off + length >
+ *     src_bytes, are bad records, each counted once.  Any of them makes the call
+ *     GEVWS_ERR_INVALID on the device: `errors` is the count, the other fields
+ *     are zero and nothing else is written.  The checks run before anything is
+ *     loaded from `off` or indexed by `conn`.
+ *   - Invalid calls.  A NULL ctx, any bit of `flags`, a NULL output (d_changes,
+ *     d_change_of, d_summary), max_messages or max_changes >= 2^32 is
+ *     GEVWS_ERR_INVALID from the call, before any device is touched, even with
+ *     every pointer NULL.  With max_messages > 0 so is a NULL d_bodies,
+ *     d_msg_summary or d_join_summary, a NULL d_out with src_bytes > 0 and a
+ *     d_out that is not 16-byte aligned.
+ *
+ * Timing.  The update runs between passes, so a command takes effect at the
+ * next pass:
+ *   - a message behind "/join 3" in the same pass still goes to the old room
+ *     (to nobody, from a connection that had none);
+ *   - a command behind its connection's cut was stripped by the control step
+ *     (GEVWS_MSG_ERR_CLOSED) and is no command;
+ *   - a command in front of a close in the same pass is emitted, and the
+ *     update's rule that a close beats a join settles it;
+ *   - two commands of one connection in one pass: the last one wins.
+ *
+ * gevws_room_command_parse: the rule on host memory (FFI callers, CPU tests).
+ * body[0, length) is read and nothing else; a length outside 6..16 reads
+ * nothing.  Returns 0 for no command, 1 for a change and 2 for a rejected
+ * command, or GEVWS_ERR_INVALID for a NULL body with a length of 6..16.  *room
+ * (may be NULL) is the change's room -- GEVWS_ROOM_NONE for a leave -- and
+ * GEVWS_ROOM_NONE whenever the result is not 1. */
+enum { GEVWS_MSG_COMMAND = 10 };   /* continues the GEVWS_MSG_* enum: gevws_body.status of a stripped command */
+int gevws_room_commands_async(gevws_ctx *ctx, void *stream, gevws_body *d_bodies, uint64_t max_messages,
+                              const gevws_summary *d_msg_summary, const gevws_summary *d_join_summary,
+                              const gevws_summary *d_ctl_summary /* may be NULL */, const uint8_t *d_out,
+                              uint64_t src_bytes, uint32_t n_conns, uint32_t n_rooms, uint32_t flags,
+                              gevws_room_change *d_changes, uint64_t max_changes,
+                              int64_t *d_change_of /* max_messages entries */, gevws_summary *d_summary);
+int gevws_room_command_parse(const uint8_t *body, uint64_t length, uint32_t n_rooms, uint32_t *room /* may be NULL */);
+
 /* Outbound fragmentation: a frame size limit for what the chain sends (RFC
  * 6455 section 5.4; the reference writes every message as one frame,
  * write.go:48-84).  Additions to ABI version 3: nothing above changes.  Two
