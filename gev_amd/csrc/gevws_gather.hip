@@ -16,14 +16,14 @@
 //                     decreases, one for every record and the total behind them),
 //                     the output-tile -> entry map
 //   k_gather_spans    one lane per connection: d_conn_buf from edst
-//   k_send_gather     the copy, on k_join_copy's plan (gevws_join.hip): every
-//                     workgroup a contiguous run of 4 KiB output tiles, a tile a
-//                     step per wave; inside one segment two aligned non-temporal
-//                     16-byte loads + funnel16, aligned non-temporal stores;
-//                     every other vector assembled by its lane, entry by entry
+//   k_send_gather     the copy: the segmented copy k_join_copy runs too
+//                     (gevws_segcopy.hpp), an entry a segment; every workgroup a
+//                     contiguous run of 4 KiB output tiles, its four waves four
+//                     tiles a step
 // Nothing but the summary is written before the verdict.  Only k_send_gather
 // touches reply bytes: len read, len rounded up to 16 a span written.
 #include "gevws_internal.hpp"
+#include "gevws_segcopy.hpp"
 
 namespace {
 
@@ -35,14 +35,6 @@ static_assert(sizeof(gevws_conn_send) == 32 && offsetof(gevws_conn_send, count) 
 static_assert(sizeof(gevws_conn_buf) == 32 && offsetof(gevws_conn_buf, bytes) == 8 &&
                   offsetof(gevws_conn_buf, flags) == 16 && offsetof(gevws_conn_buf, reserved) == 20,
               "gevws_conn_buf layout");
-
-constexpr int kGatherBlock = 256;  // k_send_gather: four waves
-constexpr int kGatherWaves = kGatherBlock / 64;
-constexpr int kGatherVecs = (int)(kTile / (64 * 16));  // vectors a lane and tile: a wave takes a whole tile
-constexpr int kGatherWgPerCU = 4;  // four waves a SIMD, the whole grid resident
-static_assert(kGatherVecs == 4, "one tile = four 1 KiB rows of a wave");
-constexpr int kGatherRounds = 4;   // segments of one tile a wave takes as whole rows ...
-constexpr uint64_t kGatherRowBytes = 1024;  // ... while they are at least this long; shorter ones lane by lane
 
 // The three wires: base and readable bytes.
 struct GatherWires {
@@ -87,11 +79,6 @@ inline GatherScratch gather_scratch(void* base, uint64_t max_sends, uint32_t n_c
   return s;
 }
 
-// The entries of the call: the plan's count, none when it failed.
-__device__ __forceinline__ uint64_t gather_count(uint64_t max_sends, const gevws_summary* __restrict__ plan) {
-  return gated_count(max_sends, plan);
-}
-
 // ------------------------------------------------------------------ 1. checks and sizes
 struct GatherDec {
   uint64_t len, padded;  // its bytes; with the span's pad when it is its connection's last entry
@@ -121,7 +108,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_gather_size(const gevws_send* __
                                                             uint32_t n_conns, const gevws_summary* __restrict__ plan,
                                                             GatherWires w, uint64_t* __restrict__ acc,
                                                             uint64_t* __restrict__ blk) {
-  const uint64_t n = gather_count(max_sends, plan);
+  const uint64_t n = gated_count(max_sends, plan);
   const uint64_t k = (uint64_t)blockIdx.x * kWalkBlock + threadIdx.x;
   uint64_t vals[4] = {0, 0, 0, 0};  // entries, padded bytes, lengths, malformed entries
   uint64_t add = 0;
@@ -152,7 +139,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_gather_conns(uint64_t max_sends,
                                                              uint32_t n_conns, const gevws_summary* __restrict__ plan,
                                                              const uint64_t* __restrict__ acc,
                                                              uint64_t* __restrict__ ctl) {
-  const uint64_t n = gather_count(max_sends, plan);
+  const uint64_t n = gated_count(max_sends, plan);
   const uint32_t c = blockIdx.x * kWalkBlock + threadIdx.x;
   uint64_t bad = 0;
   if (n && c < n_conns) {
@@ -176,7 +163,7 @@ __global__ void k_gather_verdict(uint64_t max_sends, const gevws_summary* __rest
   const gevws_summary s = *sum;
   gevws_summary o;
   memset(&o, 0, sizeof(o));
-  if (gather_count(max_sends, plan)) {
+  if (gated_count(max_sends, plan)) {
     if (s.errors || ctl[0]) {
       o.errors = s.errors + ctl[0];
       o.status = GEVWS_ERR_INVALID;
@@ -199,7 +186,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_gather_place(const gevws_send* _
                                                              uint64_t* __restrict__ edst,
                                                              uint32_t* __restrict__ tile_ent) {
   if (sum->status != GEVWS_OK) return;  // capacity or a malformed record: nothing written
-  const uint64_t n = gather_count(max_sends, plan);
+  const uint64_t n = gated_count(max_sends, plan);
   const uint64_t k = (uint64_t)blockIdx.x * kWalkBlock + threadIdx.x;
   uint64_t padded = 0;
   if (k < n) padded = gather_decide(send, conn_send, n_conns, w, k).padded;
@@ -220,7 +207,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_gather_spans(uint64_t max_sends,
                                                              const gevws_summary* __restrict__ sum,
                                                              gevws_conn_buf* __restrict__ conn_buf) {
   if (sum->status != GEVWS_OK) return;
-  const uint64_t n = gather_count(max_sends, plan);
+  const uint64_t n = gated_count(max_sends, plan);
   const uint32_t c = blockIdx.x * kWalkBlock + threadIdx.x;
   if (!n || c >= n_conns) return;
   const gevws_conn_send cs = conn_send[c];
@@ -233,95 +220,72 @@ __global__ __launch_bounds__(kWalkBlock) void k_gather_spans(uint64_t max_sends,
 }
 
 // ------------------------------------------------------------------ 3. the copy
-struct GatherMaps {
-  const gevws_send* __restrict__ send;
-  const uint64_t* __restrict__ edst;
-  GatherWires w;
-  uint64_t n, end;  // entries; the region is d_buf[0, end)
-};
 // One entry's bytes: d_buf[ds, de) come from src[0, de - ds).
 struct GatherSeg {
   uint64_t ds, de;
   const uint8_t* src;
   uint64_t k;
 };
+// The map of the segmented copy (gevws_segcopy.hpp): an entry a segment, a
+// span's pad a gap between two.
+struct GatherMaps {
+  using Seg = GatherSeg;
+  const gevws_send* __restrict__ send;
+  const uint64_t* __restrict__ edst;
+  GatherWires w;
+  uint64_t n, end;  // entries; the region is d_buf[0, end)
 
-// Entry k (k < n) as a segment.  Tables that do not fit together -- a wire or
-// a range outside the three wires, a place outside the region -- give an empty
-// one: never an address the size pass did not check.
-__device__ __forceinline__ void gather_entry(const GatherMaps& M, uint64_t k, GatherSeg& g) {
-  const gevws_send e = M.send[k];
-  const uint64_t ds = M.edst[k];
-  const uint64_t wb = wire_bytes_of(M.w, e.wire);
-  const bool ok = e.wire <= 2 && e.off <= wb && e.len <= wb - e.off && ds <= M.end && e.len <= M.end - ds;
-  g.k = k;
-  g.ds = ds;
-  g.de = ok ? ds + e.len : ds;
-  g.src = wire_base_of(M.w, e.wire) + (ok ? e.off : 0);
-}
-
-// The entry at byte x of d_buf, among [lo, hi]: the last one that starts at or
-// before x (those before it at the same place are empty).  x may be a pad byte behind it.
-__device__ __forceinline__ void gather_lookup(const GatherMaps& M, uint64_t x, uint64_t lo, uint64_t hi, GatherSeg& g) {
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi + 1) >> 1;
-    if (M.edst[mid] <= x) lo = mid;
-    else hi = mid - 1;
+  // Entry k (k < n) as a segment.  Tables that do not fit together -- a wire or
+  // a range outside the three wires, a place outside the region -- give an empty
+  // one: never an address the size pass did not check.
+  __device__ __forceinline__ void entry(uint64_t k, Seg& g) const {
+    const gevws_send e = send[k];
+    const uint64_t ds = edst[k];
+    const uint64_t wb = wire_bytes_of(w, e.wire);
+    const bool ok = e.wire <= 2 && e.off <= wb && e.len <= wb - e.off && ds <= end && e.len <= end - ds;
+    g.k = k;
+    g.ds = ds;
+    g.de = ok ? ds + e.len : ds;
+    g.src = wire_base_of(w, e.wire) + (ok ? e.off : 0);
   }
-  gather_entry(M, lo, g);
-}
-
-__device__ __forceinline__ u32x4 gather_ld16_nt(const uint8_t* p) {
-  return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-}
-
-// The destination vector at x assembled entry by entry: each entry's part from
-// the one or two aligned source vectors that hold it (vectors with a counted
-// byte only), pad bytes zero.  seed: a segment that may hold x (the wave's
-// current one), or null.
-__device__ __forceinline__ u32x4 gather_vector(const GatherMaps& M, uint64_t x, uint64_t lo, uint64_t hi,
-                                               const GatherSeg* seed) {
-  GatherSeg g;
-  if (seed && x >= seed->ds && x < seed->de) g = *seed;
-  else gather_lookup(M, x, lo, hi, g);
-  u128 acc = 0;
-  uint64_t p = x;
-  const uint64_t xe = x + 16;
-  for (;;) {
-    if (p >= g.ds && p < g.de) {
-      const uint64_t stop = g.de < xe ? g.de : xe;
-      const uint32_t cnt = (uint32_t)(stop - p);  // 1..16 bytes of this entry
-      const uint8_t* sa = g.src + (p - g.ds);
-      const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(sa) & 15);
-      const uint8_t* a0 = sa - mis;
-      u128 w = u128_of(gather_ld16_nt(a0)) >> (8 * mis);
-      if (mis + cnt > 16) w |= u128_of(gather_ld16_nt(a0 + 16)) << (8 * (16 - mis));
-      if (cnt < 16) w &= (((u128)1) << (8 * cnt)) - 1;
-      acc |= w << (8 * (uint32_t)(p - x));
-      p = stop;
+  // The entry at byte x of d_buf, among [lo, hi]: the last one that starts at or
+  // before x (those before it at the same place are empty); false: x is a pad byte behind it.
+  __device__ __forceinline__ bool find(uint64_t x, uint64_t lo, uint64_t hi, Seg& g) const {
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi + 1) >> 1;
+      if (edst[mid] <= x) lo = mid;
+      else hi = mid - 1;
     }
-    if (p >= xe || g.k + 1 >= M.n) break;
-    gather_entry(M, g.k + 1, g);  // (bounded by the entry count)
-    if (g.ds >= xe) break;
-    if (g.ds > p) p = g.ds;  // a span's pad
+    entry(lo, g);
+    return x >= g.ds && x < g.de;
   }
-  return u32x4_of(acc);
-}
+  // The next entry with bytes (bounded by the entry count).
+  __device__ __forceinline__ bool next(Seg& g) const {
+    while (g.k + 1 < n) {
+      entry(g.k + 1, g);
+      if (g.de > g.ds) return true;
+    }
+    return false;
+  }
+  // A tile's first byte: the tile map's own entry, no bisection.
+  __device__ __forceinline__ bool seek(uint64_t, uint64_t lo, uint64_t, bool, Seg& g) const {
+    entry(lo, g);
+    return true;
+  }
+  static __device__ __forceinline__ void uniform(Seg& g) {
+    g.ds = uniform64(g.ds), g.de = uniform64(g.de), g.k = uniform64(g.k);
+    g.src = reinterpret_cast<const uint8_t*>(uniform64(reinterpret_cast<uintptr_t>(g.src)));
+  }
+};
 
-// A segment's fields in SGPRs (every lane computed the same ones).
-__device__ __forceinline__ void uniform_seg(GatherSeg& g) {
-  g.ds = uniform64(g.ds), g.de = uniform64(g.de), g.k = uniform64(g.k);
-  g.src = reinterpret_cast<const uint8_t*>(uniform64(reinterpret_cast<uintptr_t>(g.src)));
-}
-
-__global__ __launch_bounds__(kGatherBlock) void k_send_gather(const gevws_send* __restrict__ send, uint64_t max_sends,
-                                                              const gevws_summary* __restrict__ plan, GatherWires w,
-                                                              const uint64_t* __restrict__ edst,
-                                                              const uint32_t* __restrict__ tile_ent,
-                                                              const gevws_summary* __restrict__ sum,
-                                                              uint8_t* __restrict__ out) {
+__global__ __launch_bounds__(kSegBlock) void k_send_gather(const gevws_send* __restrict__ send, uint64_t max_sends,
+                                                           const gevws_summary* __restrict__ plan, GatherWires w,
+                                                           const uint64_t* __restrict__ edst,
+                                                           const uint32_t* __restrict__ tile_ent,
+                                                           const gevws_summary* __restrict__ sum,
+                                                           uint8_t* __restrict__ out) {
   if (sum->status != GEVWS_OK) return;
-  const uint64_t n = gather_count(max_sends, plan), end = sum->payload_bytes;  // (end is on 16)
+  const uint64_t n = gated_count(max_sends, plan), end = sum->payload_bytes;  // (end is on 16)
   if (n == 0 || end == 0) return;
   const GatherMaps M{send, edst, w, n, end};
   const uint64_t ntiles = (end + kTile - 1) / kTile;
@@ -329,60 +293,7 @@ __global__ __launch_bounds__(kGatherBlock) void k_send_gather(const gevws_send* 
   const uint64_t q = ntiles / gridDim.x, r = ntiles % gridDim.x;
   const uint64_t r0 = (uint64_t)blockIdx.x * q + (blockIdx.x < r ? blockIdx.x : r);
   const uint64_t r1 = r0 + q + (blockIdx.x < r ? 1 : 0);
-  const uint32_t wv = uniform32(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  GatherSeg g;  // the wave's current segment, kept from tile to tile (wave-uniform)
-  memset(&g, 0, sizeof(g));
-  bool have = false;
-  for (uint64_t t = r0 + wv; t < r1; t += kGatherWaves) {
-    const uint64_t T = t * kTile;
-    uint64_t lo = tile_ent[t], hi = t + 1 < ntiles ? (uint64_t)tile_ent[t + 1] : n - 1;
-    lo = lo < n ? lo : n - 1;
-    hi = hi < n ? (hi > lo ? hi : lo) : n - 1;
-    if (!(have && T >= g.ds && T < g.de)) {  // the entry at the tile's first byte: the map's own
-      gather_entry(M, lo, g);
-      uniform_seg(g);
-      have = true;
-    }
-    uint32_t done = 0;  // bit u: this lane's vector u is stored
-    for (int round = 0; g.de - g.ds >= kGatherRowBytes && round < kGatherRounds; ++round) {
-      // inside one segment the source is a constant byte shift off alignment (every x is on 16)
-      const uint32_t mis = (uint32_t)((reinterpret_cast<uintptr_t>(g.src) - g.ds) & 15);
-      uint64_t x[kGatherVecs];
-      bool fast[kGatherVecs];
-      u32x4 v0[kGatherVecs], v1[kGatherVecs];
-#pragma unroll
-      for (int u = 0; u < kGatherVecs; ++u) {
-        x[u] = T + (uint64_t)u * 1024 + (uint64_t)lane * 16;
-        fast[u] = !((done >> u) & 1) && x[u] >= g.ds && x[u] + 16 <= g.de && x[u] < end;
-        if (fast[u]) {
-          const uint8_t* a0 = g.src + (x[u] - g.ds) - mis;
-          v0[u] = gather_ld16_nt(a0);
-          if (mis) v1[u] = gather_ld16_nt(a0 + 16);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kGatherVecs; ++u)
-        if (fast[u]) st16_nt(out + x[u], mis ? funnel16(v0[u], v1[u], mis) : v0[u]), done |= 1u << u;
-      if (g.de >= T + kTile) break;
-      // the vector the segment's end cuts starts inside it: no lookup for that one
-#pragma unroll 1
-      for (int u = 0; u < kGatherVecs; ++u) {
-        const uint64_t xu = T + (uint64_t)u * 1024 + (uint64_t)lane * 16;
-        if (!((done >> u) & 1) && xu < end && xu >= g.ds && xu < g.de)
-          st16_nt(out + xu, gather_vector(M, xu, lo, hi, &g)), done |= 1u << u;
-      }
-      // on to the next entry while entries are long enough for whole rows of the wave
-      if (g.k + 1 >= n) break;
-      gather_entry(M, g.k + 1, g);
-      uniform_seg(g);
-    }
-    // what no round covered: short entries, a span's end and pad, the next span's start
-#pragma unroll 1
-    for (int u = 0; u < kGatherVecs; ++u) {
-      const uint64_t xu = T + (uint64_t)u * 1024 + (uint64_t)lane * 16;
-      if (!((done >> u) & 1) && xu < end) st16_nt(out + xu, gather_vector(M, xu, lo, hi, nullptr));
-    }
-  }
+  seg_copy_tiles(M, tile_ent, n, 0, end, r0 + uniform32(threadIdx.x >> 6), r1, kSegWaves, out);
 }
 
 }  // namespace
@@ -426,8 +337,8 @@ extern "C" int gevws_send_gather_async(gevws_ctx* ctx, void* stream, const gevws
   k_gather_place<<<nblk, kWalkBlock, 0, st>>>(d_send, max_sends, d_conn_send, n_conns, d_plan, w, s.blk, d_summary,
                                               s.edst, s.tile_ent);
   k_gather_spans<<<nblkc, kWalkBlock, 0, st>>>(max_sends, d_conn_send, n_conns, d_plan, s.edst, d_summary, d_conn_buf);
-  k_send_gather<<<(uint32_t)ctx->num_cus * kGatherWgPerCU, kGatherBlock, 0, st>>>(d_send, max_sends, d_plan, w, s.edst,
-                                                                                 s.tile_ent, d_summary, d_buf);
+  k_send_gather<<<(uint32_t)ctx->num_cus * kSegWgPerCU, kSegBlock, 0, st>>>(d_send, max_sends, d_plan, w, s.edst,
+                                                                            s.tile_ent, d_summary, d_buf);
   GEVWS_HIP(hipGetLastError());
   return mark_last(ctx, st);
 }

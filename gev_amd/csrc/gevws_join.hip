@@ -12,11 +12,9 @@
 //   k_join_place   one lane per message: d_bodies, and for a copied message
 //                  its place (mdst), its frames' span, each frame's running
 //                  offset inside the message (foff), the output-tile -> message map
-//   k_join_copy    the gather: every workgroup a contiguous run of 4 KiB output
-//                  tiles, a quarter of it a wave, a tile a wave step; aligned
-//                  16-byte non-temporal stores, two aligned loads + funnel16
-//                  inside a fragment, vectors that straddle fragments assembled
-//                  from each fragment's bytes
+//   k_join_copy    the gather: the segmented copy k_send_gather runs too
+//                  (gevws_segcopy.hpp), a fragment a segment; every workgroup a
+//                  contiguous run of 4 KiB output tiles, a quarter of it a wave
 // Only k_join_copy touches payload bytes: L read, L rounded up to 16 written a
 // copied body.
 //
@@ -32,6 +30,7 @@
 // k_reply_emit, an order-preserving compaction of the delivered bodies into the
 // two lists (fields 0 and 1 of the block partials are the two lists' counts).
 #include "gevws_internal.hpp"
+#include "gevws_segcopy.hpp"
 
 namespace {
 
@@ -41,14 +40,7 @@ static_assert(sizeof(gevws_body) == 32 && offsetof(gevws_body, length) == 8 && o
 static_assert(sizeof(gevws_inflated) == 32 && sizeof(gevws_deflate_msg) == 24 && sizeof(gevws_out_frame) == 32,
               "record layouts");
 
-constexpr int kJoinBlock = 256;    // k_join_copy: four waves
-constexpr int kJoinWaves = kJoinBlock / 64;
-constexpr int kJoinVecs = (int)(kTile / (64 * 16));  // vectors a lane and tile: a wave takes a whole tile
-constexpr int kJoinWgPerCU = 4;   // 98 VGPRs: four waves a SIMD, the whole grid resident
-static_assert(kJoinVecs == 4, "one tile = four 1 KiB rows of a wave");
-constexpr int kJoinWalk = 4;      // fragments a wave steps forward to reach a tile's first byte before it bisects
-constexpr int kJoinRounds = 4;    // fragments of one tile a wave takes as whole rows ...
-constexpr uint64_t kJoinRowBytes = 1024;  // ... while they are at least this long; shorter ones lane by lane
+constexpr int kJoinWalk = 4;  // fragments a wave steps forward to reach a tile's first byte before it bisects
 
 // ------------------------------------------------------------------ scratch
 // What a copied body has beside its frames: the first `pre` bytes come from
@@ -302,7 +294,17 @@ __global__ __launch_bounds__(kWalkBlock) void k_join_place(const gevws_frame* __
 }
 
 // ------------------------------------------------------------------ 3. the gather
+// One fragment's counted bytes: d_out[ds, de) come from src[0, de - ds).
+struct JoinFrag {
+  uint64_t ds, de;
+  const uint8_t* src;
+  uint64_t m, f, last, body_end;  // its message and frame, the message's last frame, the end of its body in d_out
+};
+// The map of the segmented copy (gevws_segcopy.hpp): a fragment a segment,
+// the tile map's entries messages, no gap inside a body.
+template <bool CARRY>
 struct JoinMaps {
+  using Seg = JoinFrag;
   const gevws_frame* __restrict__ fr;
   const int64_t* __restrict__ msg_of;
   const gevws_body* __restrict__ bodies;
@@ -315,202 +317,109 @@ struct JoinMaps {
   const JoinExt* __restrict__ ext;
   const uint8_t* __restrict__ carry_src;
   uint64_t carry_src_bytes;
-};
-// One fragment's counted bytes: d_out[ds, de) come from src[0, de - ds).
-struct JoinFrag {
-  uint64_t ds, de;
-  const uint8_t* src;
-  uint64_t m, f, last, body_end;  // its message and frame, the message's last frame, the end of its body in d_out
-};
 
-// The fragment that holds byte x of d_out, x inside a copied body of a
-// message in [mlo, mhi]; false: x is a pad byte.
-template <bool CARRY>
-__device__ __forceinline__ bool join_lookup(const JoinMaps& M, uint64_t x, uint64_t mlo, uint64_t mhi, JoinFrag& g) {
-  uint64_t lo = mlo, hi = mhi;
-  while (lo < hi) {  // the last message that starts at or before x: the later ones at its place take no space
-    const uint64_t mid = (lo + hi + 1) >> 1;
-    if (M.mdst[mid] <= x) lo = mid;
-    else hi = mid - 1;
-  }
-  const gevws_body b = M.bodies[lo];
-  if (!(b.flags & GEVWS_BODY_JOINED) || x < b.off || x - b.off >= b.length) return false;
-  const uint64_t pos = x - b.off;
-  const uint2 sp = M.span[lo];
-  uint64_t flo = sp.x, fhi = sp.y;
-  uint64_t owner = lo;  // the message its frames map to in msg_of
-  if constexpr (CARRY) {
-    const JoinExt e = M.ext[lo];
-    owner = e.msg;
-    if (pos < e.pre) {  // below foff[first_frame]: the prefix, a fragment whose successor is first_frame
-      if (e.psrc > M.carry_src_bytes || e.pre > M.carry_src_bytes - e.psrc) return false;
-      const bool frames = flo <= fhi && fhi < M.nframes;
-      g.ds = b.off, g.de = b.off + e.pre;
-      g.src = M.carry_src + e.psrc;
-      g.m = owner, g.f = frames ? flo - 1 : 1, g.last = frames ? fhi : 0, g.body_end = b.off + b.length;
-      return true;
+  // The fragment that holds byte x of d_out, x inside a copied body of a
+  // message in [mlo, mhi]; false: x is a pad byte.
+  __device__ __forceinline__ bool find(uint64_t x, uint64_t mlo, uint64_t mhi, Seg& g) const {
+    uint64_t lo = mlo, hi = mhi;
+    while (lo < hi) {  // the last message that starts at or before x: the later ones at its place take no space
+      const uint64_t mid = (lo + hi + 1) >> 1;
+      if (mdst[mid] <= x) lo = mid;
+      else hi = mid - 1;
     }
-  }
-  if (fhi >= M.nframes || flo > fhi) return false;
-  const uint64_t last = fhi;
-  while (flo < fhi) {  // the last frame that starts at or before pos: it holds the byte
-    const uint64_t mid = (flo + fhi + 1) >> 1;
-    if (M.foff[mid] <= pos) flo = mid;
-    else fhi = mid - 1;
-  }
-  const gevws_frame rec = M.fr[flo];
-  const uint64_t fo = M.foff[flo], len = (uint64_t)rec.hdr.length;
-  if (pos < fo || pos - fo >= len) return false;
-  g.ds = b.off + fo;
-  g.de = g.ds + len;
-  g.src = M.payload + rec.payload_off;
-  g.m = owner, g.f = flo, g.last = last, g.body_end = b.off + b.length;
-  return true;
-}
-
-__device__ __forceinline__ u32x4 ld16_nt(const uint8_t* p) {
-  return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-}
-
-// The destination vector at x assembled byte range by byte range: each
-// fragment's part from the one or two aligned source vectors that hold it
-// (vectors with a counted byte only), bytes past the body zero.
-// g -> the message's next fragment with bytes, which follows it in d_out; false: g was the last.
-__device__ __forceinline__ bool join_next(const JoinMaps& M, JoinFrag& g) {
-  for (uint64_t f = g.f + 1; f <= g.last; ++f) {
-    const gevws_frame rec = M.fr[f];
-    const uint64_t len = (uint64_t)rec.hdr.length;
-    if (len && M.msg_of[f] == (int64_t)g.m) {
-      g.f = f;
-      g.ds = g.de, g.de = g.ds + len;
-      g.src = M.payload + rec.payload_off;
-      return true;
+    const gevws_body b = bodies[lo];
+    if (!(b.flags & GEVWS_BODY_JOINED) || x < b.off || x - b.off >= b.length) return false;
+    const uint64_t pos = x - b.off;
+    const uint2 sp = span[lo];
+    uint64_t flo = sp.x, fhi = sp.y;
+    uint64_t owner = lo;  // the message its frames map to in msg_of
+    if constexpr (CARRY) {
+      const JoinExt e = ext[lo];
+      owner = e.msg;
+      if (pos < e.pre) {  // below foff[first_frame]: the prefix, a fragment whose successor is first_frame
+        if (e.psrc > carry_src_bytes || e.pre > carry_src_bytes - e.psrc) return false;
+        const bool frames = flo <= fhi && fhi < nframes;
+        g.ds = b.off, g.de = b.off + e.pre;
+        g.src = carry_src + e.psrc;
+        g.m = owner, g.f = frames ? flo - 1 : 1, g.last = frames ? fhi : 0, g.body_end = b.off + b.length;
+        return true;
+      }
     }
+    if (fhi >= nframes || flo > fhi) return false;
+    const uint64_t last = fhi;
+    while (flo < fhi) {  // the last frame that starts at or before pos: it holds the byte
+      const uint64_t mid = (flo + fhi + 1) >> 1;
+      if (foff[mid] <= pos) flo = mid;
+      else fhi = mid - 1;
+    }
+    const gevws_frame rec = fr[flo];
+    const uint64_t fo = foff[flo], len = (uint64_t)rec.hdr.length;
+    if (pos < fo || pos - fo >= len) return false;
+    g.ds = b.off + fo;
+    g.de = g.ds + len;
+    g.src = payload + rec.payload_off;
+    g.m = owner, g.f = flo, g.last = last, g.body_end = b.off + b.length;
+    return true;
   }
-  return false;
-}
-
-// seed: a fragment that may hold x (the wave's current one), or null.
-template <bool CARRY>
-__device__ __forceinline__ u32x4 join_vector(const JoinMaps& M, uint64_t x, uint64_t mlo, uint64_t mhi,
-                                             const JoinFrag* seed) {
-  JoinFrag g;
-  if (seed && x >= seed->ds && x < seed->de) g = *seed;
-  else if (!join_lookup<CARRY>(M, x, mlo, mhi, g)) return u32x4{0, 0, 0, 0};  // a whole vector of pad
-  u128 acc = 0;
-  uint64_t p = x;
-  for (;;) {
-    const uint64_t stop = g.de < x + 16 ? g.de : x + 16;
-    const uint32_t cnt = (uint32_t)(stop - p);  // 1..16 bytes of this fragment
-    const uint8_t* sa = g.src + (p - g.ds);
-    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(sa) & 15);
-    const uint8_t* a0 = sa - mis;
-    u128 w = u128_of(ld16_nt(a0)) >> (8 * mis);
-    if (mis + cnt > 16) w |= u128_of(ld16_nt(a0 + 16)) << (8 * (16 - mis));
-    if (cnt < 16) w &= (((u128)1) << (8 * cnt)) - 1;
-    acc |= w << (8 * (uint32_t)(p - x));
-    p = stop;
-    if (p >= x + 16 || p >= g.body_end) break;
-    if (!join_next(M, g)) break;  // (not a table the place kernel writes)
+  // g -> the message's next fragment with bytes, which follows it in d_out; false: g was the last.
+  // (Not a table the place kernel writes: control frames and empty fragments are skipped here.)
+  __device__ __forceinline__ bool next(Seg& g) const {
+    if (g.de >= g.body_end) return false;
+    for (uint64_t f = g.f + 1; f <= g.last; ++f) {
+      const gevws_frame rec = fr[f];
+      const uint64_t len = (uint64_t)rec.hdr.length;
+      if (len && msg_of[f] == (int64_t)g.m) {
+        g.f = f;
+        g.ds = g.de, g.de = g.ds + len;
+        g.src = payload + rec.payload_off;
+        return true;
+      }
+    }
+    return false;
   }
-  return u32x4_of(acc);
-}
-
-// A fragment's fields in SGPRs (every lane computed the same ones).
-__device__ __forceinline__ void uniform_frag(JoinFrag& g) {
-  g.ds = uniform64(g.ds), g.de = uniform64(g.de);
-  g.src = reinterpret_cast<const uint8_t*>(uniform64(reinterpret_cast<uintptr_t>(g.src)));
-  g.m = uniform64(g.m), g.f = uniform64(g.f), g.last = uniform64(g.last), g.body_end = uniform64(g.body_end);
-}
+  // A tile's first byte: a few long fragments on in the same body, then the bisections.
+  __device__ __forceinline__ bool seek(uint64_t T, uint64_t mlo, uint64_t mhi, bool have, Seg& g) const {
+    if (have && T >= g.de && T < g.body_end && g.de - g.ds >= kSegRowBytes)
+      for (int k = 0; k < kJoinWalk && next(g); ++k)
+        if (T < g.de) return true;
+    return find(T, mlo, mhi, g);
+  }
+  // A fragment's fields in SGPRs (every lane computed the same ones).
+  static __device__ __forceinline__ void uniform(Seg& g) {
+    g.ds = uniform64(g.ds), g.de = uniform64(g.de);
+    g.src = reinterpret_cast<const uint8_t*>(uniform64(reinterpret_cast<uintptr_t>(g.src)));
+    g.m = uniform64(g.m), g.f = uniform64(g.f), g.last = uniform64(g.last), g.body_end = uniform64(g.body_end);
+  }
+};
 
 template <bool CARRY>
-__global__ __launch_bounds__(kJoinBlock) void k_join_copy(const gevws_frame* __restrict__ fr, uint64_t max_frames,
-                                                          const int64_t* __restrict__ msg_of,
-                                                          const uint8_t* __restrict__ payload,
-                                                          const gevws_body* __restrict__ bodies,
-                                                          const uint64_t* __restrict__ mdst,
-                                                          const uint2* __restrict__ span,
-                                                          const uint64_t* __restrict__ foff,
-                                                          const uint32_t* __restrict__ tile_msg,
-                                                          const uint64_t* __restrict__ ctl,
-                                                          const gevws_summary* __restrict__ sum,
-                                                          uint8_t* __restrict__ out,
-                                                          const gevws_summary* __restrict__ other_sum,
-                                                          const JoinExt* __restrict__ ext,
-                                                          const uint8_t* __restrict__ carry_src,
-                                                          uint64_t carry_src_bytes) {
+__global__ __launch_bounds__(kSegBlock) void k_join_copy(const gevws_frame* __restrict__ fr, uint64_t max_frames,
+                                                         const int64_t* __restrict__ msg_of,
+                                                         const uint8_t* __restrict__ payload,
+                                                         const gevws_body* __restrict__ bodies,
+                                                         const uint64_t* __restrict__ mdst,
+                                                         const uint2* __restrict__ span,
+                                                         const uint64_t* __restrict__ foff,
+                                                         const uint32_t* __restrict__ tile_msg,
+                                                         const uint64_t* __restrict__ ctl,
+                                                         const gevws_summary* __restrict__ sum,
+                                                         uint8_t* __restrict__ out,
+                                                         const gevws_summary* __restrict__ other_sum,
+                                                         const JoinExt* __restrict__ ext,
+                                                         const uint8_t* __restrict__ carry_src,
+                                                         uint64_t carry_src_bytes) {
   if (sum->status != GEVWS_OK) return;
   if constexpr (CARRY)
     if (other_sum->status != GEVWS_OK) return;  // either side failing suppresses both
   const uint64_t base = ctl[0], n = ctl[1], end = sum->payload_bytes;  // the joined region is d_out[base, end)
   if (end <= base || n == 0) return;
-  const JoinMaps M{fr, msg_of, bodies, mdst, span, foff, payload, max_frames, ext, carry_src, carry_src_bytes};
+  const JoinMaps<CARRY> M{fr, msg_of, bodies, mdst, span, foff, payload, max_frames, ext, carry_src, carry_src_bytes};
   const uint64_t ntiles = (end - base + kTile - 1) / kTile;
   // a workgroup's run of tiles is its four waves' runs, one behind the other
-  const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint64_t nw = (uint64_t)gridDim.x * kJoinWaves, gw = (uint64_t)blockIdx.x * kJoinWaves + wv;
+  const uint64_t nw = (uint64_t)gridDim.x * kSegWaves, gw = (uint64_t)blockIdx.x * kSegWaves + (threadIdx.x >> 6);
   const uint64_t per = (ntiles + nw - 1) / nw;
   const uint64_t t0 = gw * per, t1 = t0 + per < ntiles ? t0 + per : ntiles;
-  JoinFrag g;  // the wave's current fragment, kept from tile to tile (wave-uniform)
-  memset(&g, 0, sizeof(g));
-  bool have = false;
-  for (uint64_t t = t0; t < t1; ++t) {
-    const uint64_t T = base + t * kTile;
-    uint64_t mlo = tile_msg[t], mhi = t + 1 < ntiles ? (uint64_t)tile_msg[t + 1] : n - 1;
-    mlo = mlo < n ? mlo : n - 1;
-    mhi = mhi < n ? (mhi > mlo ? mhi : mlo) : n - 1;
-    if (!(have && T >= g.ds && T < g.de)) {  // the fragment at the tile's first byte
-      bool found = false;
-      // a few long fragments on in the same body: no bisection
-      if (have && T >= g.de && T < g.body_end && g.de - g.ds >= kJoinRowBytes)
-        for (int k = 0; k < kJoinWalk && !found && join_next(M, g); ++k) found = T < g.de;
-      if (!found) found = join_lookup<CARRY>(M, T, mlo, mhi, g);
-      have = found;
-      uniform_frag(g);
-    }
-    uint32_t done = 0;  // bit u: this lane's vector u is stored
-    for (int round = 0; have && g.de - g.ds >= kJoinRowBytes && round < kJoinRounds; ++round) {
-      // inside one fragment the source is a constant byte shift off alignment
-      const uint32_t mis = (uint32_t)((reinterpret_cast<uintptr_t>(g.src) + (T - g.ds)) & 15);
-      uint64_t x[kJoinVecs];
-      bool fast[kJoinVecs];
-      u32x4 v0[kJoinVecs], v1[kJoinVecs];
-#pragma unroll
-      for (int u = 0; u < kJoinVecs; ++u) {
-        x[u] = T + (uint64_t)u * 1024 + (uint64_t)lane * 16;
-        // (end is on 16: a vector that starts below it is inside)
-        fast[u] = !((done >> u) & 1) && x[u] >= g.ds && x[u] + 16 <= g.de && x[u] < end;
-        if (fast[u]) {
-          const uint8_t* a0 = g.src + (x[u] - g.ds) - mis;
-          v0[u] = ld16_nt(a0);
-          if (mis) v1[u] = ld16_nt(a0 + 16);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kJoinVecs; ++u)
-        if (fast[u]) st16_nt(out + x[u], mis ? funnel16(v0[u], v1[u], mis) : v0[u]), done |= 1u << u;
-      if (g.de >= T + kTile) break;
-      // the vector the fragment's end cuts starts inside it: no lookup for that one
-#pragma unroll 1
-      for (int u = 0; u < kJoinVecs; ++u) {
-        const uint64_t xu = T + (uint64_t)u * 1024 + (uint64_t)lane * 16;
-        if (!((done >> u) & 1) && xu < end && xu >= g.ds && xu < g.de)
-          st16_nt(out + xu, join_vector<CARRY>(M, xu, mlo, mhi, &g)), done |= 1u << u;
-      }
-      // on to the body's next fragment while fragments are long enough for whole rows of the wave
-      if (!join_next(M, g)) {
-        have = false;
-        break;
-      }
-      uniform_frag(g);
-    }
-    // what no round covered: short fragments, a body's pad, the next body's start
-#pragma unroll 1
-    for (int u = 0; u < kJoinVecs; ++u) {
-      const uint64_t xu = T + (uint64_t)u * 1024 + (uint64_t)lane * 16;
-      if (!((done >> u) & 1) && xu < end) st16_nt(out + xu, join_vector<CARRY>(M, xu, mlo, mhi, nullptr));
-    }
-  }
+  seg_copy_tiles(M, tile_msg, n, base, end, t0, t1, 1, out);
 }
 
 // ------------------------------------------------------------------ the carry side
@@ -847,7 +756,7 @@ static int join_with_carry(gevws_ctx* ctx, hipStream_t st, const gevws_frame* d_
   const JoinScratch s = join_scratch(ctx->scratch, max_frames, max_messages, nblk, out_cap, n_conns, nblkc, carry_cap);
   const JoinCarryIn ca{d_carry_in, n_conns, max_message_bytes, carry_flags};
   const CarryIn in{d_messages, d_conn_msg, d_carry_in, carry_src_bytes, max_message_bytes, n_conns, carry_flags};
-  const uint32_t grid = (uint32_t)ctx->num_cus * kJoinWgPerCU;
+  const uint32_t grid = (uint32_t)ctx->num_cus * kSegWgPerCU;
   GEVWS_HIP(hipMemsetAsync(s.ctl, 0, s.zero_bytes, st));
   if (max_messages) {
     k_join_size<true><<<nblk, kWalkBlock, 0, st>>>(d_messages, max_messages, d_msg_summary, d_inflated,
@@ -867,12 +776,12 @@ static int join_with_carry(gevws_ctx* ctx, hipStream_t st, const gevws_frame* d_
                                               d_carry_summary, d_summary, d_carry_out, s.cbody, s.cdst, s.cspan,
                                               s.cext, s.foff, s.ctile);
   if (max_messages)
-    k_join_copy<true><<<grid, kJoinBlock, 0, st>>>(d_frames, max_frames, d_msg_of, d_payload, d_bodies, s.mdst, s.span,
-                                                   s.foff, s.tile_msg, s.ctl, d_summary, d_out, d_carry_summary,
-                                                   s.ext, d_carry_src, carry_src_bytes);
-  k_join_copy<true><<<grid, kJoinBlock, 0, st>>>(d_frames, max_frames, d_msg_of, d_payload, s.cbody, s.cdst, s.cspan,
-                                                 s.foff, s.ctile, s.cctl, d_carry_summary, d_carry_dst, d_summary,
-                                                 s.cext, d_carry_src, carry_src_bytes);
+    k_join_copy<true><<<grid, kSegBlock, 0, st>>>(d_frames, max_frames, d_msg_of, d_payload, d_bodies, s.mdst, s.span,
+                                                  s.foff, s.tile_msg, s.ctl, d_summary, d_out, d_carry_summary,
+                                                  s.ext, d_carry_src, carry_src_bytes);
+  k_join_copy<true><<<grid, kSegBlock, 0, st>>>(d_frames, max_frames, d_msg_of, d_payload, s.cbody, s.cdst, s.cspan,
+                                                s.foff, s.ctile, s.cctl, d_carry_summary, d_carry_dst, d_summary,
+                                                s.cext, d_carry_src, carry_src_bytes);
   GEVWS_HIP(hipGetLastError());
   return mark_last(ctx, st);
 }
@@ -922,7 +831,7 @@ extern "C" int gevws_join_carry_ext_async(gevws_ctx* ctx, void* stream, const ge
   k_join_place<false><<<nblk, kWalkBlock, 0, st>>>(d_frames, max_frames, d_messages, d_msg_of, d_inflated, flags,
                                                    s.ctl, s.blk, d_summary, d_bodies, s.mdst, s.span, s.foff,
                                                    s.tile_msg, none, nullptr, nullptr);
-  k_join_copy<false><<<(uint32_t)ctx->num_cus * kJoinWgPerCU, kJoinBlock, 0, st>>>(
+  k_join_copy<false><<<(uint32_t)ctx->num_cus * kSegWgPerCU, kSegBlock, 0, st>>>(
       d_frames, max_frames, d_msg_of, d_payload, d_bodies, s.mdst, s.span, s.foff, s.tile_msg, s.ctl, d_summary,
       d_out, nullptr, nullptr, nullptr, 0);
   GEVWS_HIP(hipGetLastError());

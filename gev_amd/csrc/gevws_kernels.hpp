@@ -457,6 +457,9 @@ __device__ __forceinline__ u32x4 ld16u_stream(const uint8_t* p) {
   }
 }
 
+__device__ __forceinline__ u32x4 ld16_nt(const uint8_t* p) {
+  return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+}
 __device__ __forceinline__ void st16_nt(uint8_t* p, u32x4 x) {
   __builtin_nontemporal_store(x, reinterpret_cast<u32x4*>(p));
 }
