@@ -36,6 +36,7 @@ from ._abi import (CONTROL_NO_PING_FOR_PONG, CTL_FAILED, CTL_SHUTDOWN, MSG_ERR_C
                    WIRE_PLAIN)
 from ._abi import ROOM_NONE, ROOMS_SKIP_SENDER
 from ._abi import CHANGE_NONE, CHANGE_REJECTED, MSG_COMMAND
+from ._abi import PUSH_ALL, PUSH_CONN, PUSH_ROOM
 from ._abi import (ERR_CAPACITY, ERR_DEVICE, ERR_HANDSHAKE, ERR_INVALID, ERR_LEN_MSB, ERR_NOT_UPGRADED,
                    HANDSHAKE, IN_PAD, MEM_DEFAULT, MEM_FINE, MEM_UNCACHED, NEED_MORE, OK, PAYLOAD_ALIGN,
                    SUMMARY_UNORDERED, TILE, Header)
@@ -80,6 +81,9 @@ CONN_BUF_DTYPE = np.dtype([("off", "<u8"), ("bytes", "<u8"), ("flags", "<u4"), (
 assert CONN_BUF_DTYPE.itemsize == 32
 ROOM_CHANGE_DTYPE = np.dtype([("conn", "<u4"), ("room", "<u4")])   # gevws_room_change
 assert ROOM_CHANGE_DTYPE.itemsize == 8
+PUSH_DTYPE = np.dtype([("off", "<u8"), ("length", "<u8"), ("target", "<u4"), ("kind", "u1"), ("opcode", "u1"),
+                       ("reserved", "u1", (10,))])   # gevws_push
+assert PUSH_DTYPE.itemsize == 32
 assert DEFLATE_MSG_DTYPE.itemsize == 24 and OUT_FRAME_DTYPE.itemsize == 32
 assert MSG_STATE_DTYPE.itemsize == 8 and MESSAGE_DTYPE.itemsize == 32 and CONN_MSG_DTYPE.itemsize == 32
 assert SUMMARY_DTYPE.itemsize == 64 and SYNTH_DTYPE.itemsize == 24
@@ -254,6 +258,44 @@ def room_command_parse(body: bytes, n_rooms: int) -> Tuple[int, int]:
     if st < 0:
         raise RuntimeError(f"gevws_room_command_parse: {status_string(st)}")
     return st, int(room.value)
+
+
+def push_check(records: np.ndarray, n_conns: int, n_rooms: int, src_bytes: int) -> int:
+    """gevws_push_check: how many of the PUSH_DTYPE records the push pass would
+    call malformed (a bad kind, target, opcode, range, reserved byte or a key
+    below the previous record's), by the device's rule."""
+    records = np.ascontiguousarray(records, dtype=PUSH_DTYPE).reshape(-1)
+    n = int(records.size)
+    r = lib.gevws_push_check(records.ctypes.data if n else None, n, int(n_conns), int(n_rooms), int(src_bytes))
+    if r < 0:
+        raise RuntimeError(f"gevws_push_check: {status_string(int(r))}")
+    return int(r)
+
+
+def push_records(items) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The push list of `items`, a sequence of (kind, target, opcode, bytes) ->
+    (records, arena, perm).  The bodies are laid into `arena` (uint8) in item
+    order, each on a PAYLOAD_ALIGN boundary, with IN_PAD zero bytes behind the
+    last one: the slack the encoder's and the deflate step's vector loads need
+    (the readable bytes are arena.size - IN_PAD).  `records` (PUSH_DTYPE) are
+    stable-sorted by (kind, target), as gevws_push_lists_async wants them:
+    records[k] is items[perm[k]], so pushes of one key keep their order."""
+    items = list(items)
+    n = len(items)
+    recs = np.zeros(n, PUSH_DTYPE)
+    at, bodies = 0, []
+    for i, (kind, target, opcode, body) in enumerate(items):
+        body = bytes(body)
+        recs[i]["off"], recs[i]["length"] = at, len(body)
+        recs[i]["target"], recs[i]["kind"], recs[i]["opcode"] = int(target), int(kind), int(opcode)
+        bodies.append((at, body))
+        at += (len(body) + PAYLOAD_ALIGN - 1) // PAYLOAD_ALIGN * PAYLOAD_ALIGN
+    arena = np.zeros(at + IN_PAD, np.uint8)
+    for off, body in bodies:
+        arena[off: off + len(body)] = np.frombuffer(body, np.uint8)
+    key = (recs["kind"].astype(np.uint64) << np.uint64(32)) | recs["target"].astype(np.uint64)
+    perm = np.argsort(key, kind="stable")
+    return recs[perm], arena, perm.astype(np.int64)
 
 
 def _torch():
@@ -1789,6 +1831,149 @@ class Engine:
                          send=send, conn_send=conn_send, summary=plan_sum, n_conns=n_conns, send_buf=send_buf,
                          conn_buf=conn_buf, gather_summary=gsum, plain_of=plain_of[:nm].cpu().numpy(),
                          def_of=def_of[:nm].cpu().numpy(), room_changes=room_changes)
+
+    def push_lists_async(self, pushes, max_pushes: int, prev, src_bytes: int, conn_ext, window_bits, live,
+                         n_conns: int, rooms: Optional["Rooms"], flags: int, def_msgs, def_summary, plain,
+                         plain_summary, plain_of, def_of, stream=None) -> None:
+        """gevws_push_lists_async on device tensors: every push once in the
+        plain list and once in the deflate list, as its live recipients need it.
+        rooms None: no room tables (a ROOM push is then malformed); prev: the
+        summary of whatever made the list on the device, or None."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        tabs = (None, None, None, 0, 0) if rooms is None else (
+            ptr(rooms.conn_room), ptr(rooms.room_first), ptr(rooms.room_members), rooms.n_rooms, rooms.n_members)
+        st = lib.gevws_push_lists_async(
+            self._ctx, _stream_handle(stream), ptr(pushes), max_pushes, ptr(prev), src_bytes, ptr(conn_ext),
+            ptr(window_bits), ptr(live), n_conns, *tabs, flags, ptr(def_msgs), ptr(def_summary), ptr(plain),
+            ptr(plain_summary), ptr(plain_of), ptr(def_of))
+        if st != OK:
+            raise RuntimeError(f"gevws_push_lists_async: {status_string(st)}")
+
+    def push_plan_async(self, pushes, max_pushes: int, prev, src_bytes: int, plain_summary, def_summary, plain_of,
+                        def_of, plain_off, plain_encoded, def_off, def_encoded, conn_ext, live, n_conns: int,
+                        rooms: Optional["Rooms"], flags: int, send, max_sends: int, conn_send, summary,
+                        stream=None) -> None:
+        """gevws_push_plan_async on device tensors: every push's one encoded
+        frame named once per live recipient, each recipient's in list order."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        tabs = (None, None, None, 0, 0) if rooms is None else (
+            ptr(rooms.conn_room), ptr(rooms.room_first), ptr(rooms.room_members), rooms.n_rooms, rooms.n_members)
+        st = lib.gevws_push_plan_async(
+            self._ctx, _stream_handle(stream), ptr(pushes), max_pushes, ptr(prev), src_bytes, ptr(plain_summary),
+            ptr(def_summary), ptr(plain_of), ptr(def_of), ptr(plain_off), ptr(plain_encoded), ptr(def_off),
+            ptr(def_encoded), ptr(conn_ext), ptr(live), n_conns, *tabs, flags, ptr(send), max_sends, ptr(conn_send),
+            ptr(summary))
+        if st != OK:
+            raise RuntimeError(f"gevws_push_plan_async: {status_string(st)}")
+
+    def push(self, pushes, src, conn_ext, rooms: Optional["Rooms"] = None, window_bits=None, live=None,
+             flags: int = 0, gather: bool = False, max_fragment_bytes: Optional[int] = None, stream=None, *,
+             n_conns: Optional[int] = None) -> "Responses":
+        """A push pass, messages the host originates: push_lists -> deflate (no
+        contexts) -> the two encodes -> push plan -> (gather).  pushes: the
+        sorted PUSH_DTYPE records and src their body arena, as push_records
+        returns them (numpy, uploaded; or device tensors: uint8 [n, 32] and a
+        uint8 arena whose last IN_PAD bytes are slack).  conn_ext / window_bits
+        / live: uint8 [n_conns] device tensors or None (no deflate-taker /
+        window 15 / every connection a live session); rooms: the room tables or
+        None; flags: the deflate step's.  n_conns: the connection table's size,
+        by default that of the first table given.  The result is respond's, with
+        an empty control wire: conn_bytes(c) and host_sends() work unchanged,
+        send[k].frame is the push's index in the list and plain_of / def_of its
+        place in the two lists.  max_fragment_bytes: one frame size limit for
+        every recipient; pings and pongs stay whole."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        if n_conns is None:
+            tabs = [t for t in (conn_ext, live, window_bits, rooms.conn_room if rooms is not None else None)
+                    if t is not None]
+            if not tabs:
+                raise ValueError("push: n_conns is needed when no connection table is given")
+            n_conns = int(tabs[0].numel())
+        z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        host = lambda t: t.cpu().numpy().view(SUMMARY_DTYPE)[0]  # noqa: E731
+        if not isinstance(pushes, torch.Tensor):
+            recs = np.ascontiguousarray(pushes, dtype=PUSH_DTYPE).reshape(-1)
+            pushes = torch.from_numpy(recs.view(np.uint8).reshape(-1, 32).copy()).to(dev)
+        if not isinstance(src, torch.Tensor):
+            src = torch.from_numpy(np.ascontiguousarray(src, dtype=np.uint8).copy()).to(dev)
+        n = int(pushes.numel()) // 32
+        src_bytes = int(src.numel()) - IN_PAD
+        if src_bytes < 0:
+            raise ValueError("push: src is shorter than its IN_PAD bytes of slack")
+        cap, capc = max(n, 1), max(n_conns, 1)
+        def_msgs, def_sum, plain, plain_sum = z(cap, 24), z(64), z(cap, 32), z(64)
+        plain_of = torch.full((cap,), -1, dtype=torch.int64, device=dev)
+        def_of = torch.full((cap,), -1, dtype=torch.int64, device=dev)
+        self.push_lists_async(pushes, n, None, src_bytes, conn_ext, window_bits, live, n_conns, rooms, 0, def_msgs,
+                              def_sum, plain, plain_sum, plain_of, def_of, stream)
+        torch.cuda.synchronize(self.device)
+        ds, ps = host(def_sum), host(plain_sum)
+        if int(ds["status"]) != OK or int(ps["status"]) != OK:
+            raise RuntimeError(f"push: push_lists: {status_string(int(ds['status']))} ({int(ds['errors'])} records)")
+        nd, npl = int(ds["frames"]), int(ps["frames"])
+        dm = def_msgs[:nd].cpu().numpy().reshape(-1).view(DEFLATE_MSG_DTYPE)
+        dcap = int(sum((deflate_bound(int(x)) + 15) // 16 * 16 for x in dm["length"])) + 16
+        res = Deflated(frames=z(cap, 32), out=torch.empty(dcap + _abi.OUT_PAD, dtype=torch.uint8, device=dev),
+                       summary=z(64), n_messages=nd)
+        if n:
+            self.deflate_async(def_msgs, n, def_sum, src, src_bytes, flags, res.frames, res.out, dcap, res.summary,
+                               stream)
+            torch.cuda.synchronize(self.device)
+        s = res.summary_host()
+        if int(s["status"]) != OK:
+            raise RuntimeError(f"push: deflate: {status_string(int(s['status']))}")
+        total0 = int(plain[:npl].cpu().numpy().reshape(-1).view(OUT_FRAME_DTYPE)["payload_len"].sum())
+        wires, tables, firsts = [], [], [None, None]
+        for recs, gate, payload, k, total in ((plain, plain_sum, src, npl, total0),
+                                              (res.frames, res.summary, res.out, nd, int(s["payload_len"]))):
+            if max_fragment_bytes is not None:
+                w, t, firsts[len(wires)] = self._fragmented_wire(recs, cap, gate, payload, k, total,
+                                                                 max_fragment_bytes, stream, "push")
+                wires.append(w)
+                tables.append(t)
+                continue
+            wcap = total + 14 * k + 16
+            wire = torch.empty(wcap + _abi.OUT_PAD, dtype=torch.uint8, device=dev)
+            off, esum = torch.zeros(cap, dtype=torch.int64, device=dev), z(64)
+            self.encode_replies_async(recs, cap, gate, payload, wire, wcap, off, esum, stream)
+            torch.cuda.synchronize(self.device)
+            es = host(esum)
+            if int(es["status"]) != OK:
+                raise RuntimeError(f"push: encode: {status_string(int(es['status']))}")
+            wires.append((wire[: int(es["payload_bytes"])], off[:k].cpu().numpy().astype(np.uint64)))
+            tables.append((off, esum))
+        (plain_off, plain_enc), (def_off, def_enc) = tables
+        conn_send, plan_sum = z(capc, 32), z(64)
+        max_sends = cap
+        for attempt in range(2):
+            send = z(max(max_sends, 1), 32)
+            self.push_plan_async(pushes, n, None, src_bytes, plain_sum, def_sum, plain_of, def_of, plain_off,
+                                 plain_enc, def_off, def_enc, conn_ext, live, n_conns, rooms, 0, send, max_sends,
+                                 conn_send, plan_sum, stream)
+            torch.cuda.synchronize(self.device)
+            pls = host(plan_sum)
+            if int(pls["status"]) == ERR_CAPACITY and attempt == 0:   # a fan-out: more entries than pushes
+                max_sends = int(pls["frames"])
+                continue
+            break
+        if int(pls["status"]) != OK:
+            raise RuntimeError(f"push: plan: {status_string(int(pls['status']))} ({int(pls['errors'])})")
+        none32 = np.zeros(0, np.uint32)
+        echo = Echo(def_wire=wires[1][0], def_conn=none32, def_off=wires[1][1], plain_wire=wires[0][0],
+                    plain_conn=none32, plain_off=wires[0][1], reply_of=plain_of[:n].cpu().numpy(), deflated=res,
+                    plain_first=firsts[0], def_first=firsts[1])
+        ctl_wire = z(0)
+        send_buf = conn_buf = gsum = None
+        if gather:
+            send_buf, conn_buf, gsum = self._gather(send, max_sends, conn_send, n_conns, plan_sum,
+                                                    int(pls["payload_bytes"]), (wires[0][0], wires[1][0], ctl_wire),
+                                                    stream)
+        return Responses(echo=echo, ctl_wire=ctl_wire, ctl_conn=none32, ctl_of=np.zeros(0, np.int64),
+                         msg_end=np.zeros(0, np.uint64), conn_ctl=np.zeros(n_conns, CONN_CTL_DTYPE),
+                         ctl_summary=np.zeros(1, SUMMARY_DTYPE)[0], send=send, conn_send=conn_send, summary=plan_sum,
+                         n_conns=n_conns, send_buf=send_buf, conn_buf=conn_buf, gather_summary=gsum,
+                         plain_of=plain_of[:n].cpu().numpy(), def_of=def_of[:n].cpu().numpy())
 
     def messages(self, out: "Batch", state=None, max_messages: Optional[int] = None, stream=None, *,
                  conn_ext=None) -> "Messages":

@@ -100,6 +100,8 @@ ROOMS_SKIP_SENDER = 1  # call flag of both: a sender is not sent its own message
 # room commands (gevws_room_commands_async)
 MSG_COMMAND = 10  # gevws_body.status of a stripped "/join N" or "/leave" message
 CHANGE_NONE, CHANGE_REJECTED = -1, -2  # d_change_of: no command, a join whose room is not < n_rooms
+# server push (gevws_push_lists_async, gevws_push_plan_async): gevws_push.kind
+PUSH_ALL, PUSH_ROOM, PUSH_CONN = 0, 1, 2
 
 IN_PAD = 64
 MEM_DEFAULT, MEM_FINE, MEM_UNCACHED = 0, 1, 2  # gevws_device_alloc kinds
@@ -234,6 +236,12 @@ class ConnBuf(ctypes.Structure):
                 ("reserved", ctypes.c_uint32 * 3)]
 
 
+class Push(ctypes.Structure):
+    """gevws_push: one host-originated message (gevws_push_lists_async)."""
+    _fields_ = [("off", ctypes.c_uint64), ("length", ctypes.c_uint64), ("target", ctypes.c_uint32),
+                ("kind", ctypes.c_uint8), ("opcode", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 10)]
+
+
 class Reject(ctypes.Structure):
     """gevws_reject: RejectConnectionError options (ws/errors.go:81-129)."""
     _fields_ = [("code", ctypes.c_int32), ("plain", ctypes.c_int32), ("reason", ctypes.c_void_p),
@@ -281,7 +289,7 @@ assert ctypes.sizeof(Summary) == 64 and ctypes.sizeof(SynthDesc) == 24
 assert ctypes.sizeof(MsgState) == 8 and ctypes.sizeof(Message) == 32 and ctypes.sizeof(ConnMsg) == 32
 assert ctypes.sizeof(Inflated) == 32 and ctypes.sizeof(Body) == 32 and ctypes.sizeof(Carry) == 32
 assert ctypes.sizeof(ConnCtl) == 32 and ctypes.sizeof(Send) == 32 and ctypes.sizeof(ConnSend) == 32
-assert ctypes.sizeof(ConnBuf) == 32
+assert ctypes.sizeof(ConnBuf) == 32 and ctypes.sizeof(Push) == 32
 
 P = ctypes.c_void_p
 U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -394,6 +402,13 @@ SIGNATURES = {
                                             ctypes.c_uint64, P, P]),
     "gevws_fragment_offsets_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, P, P, P, P, P]),
     "gevws_fragment_records": (ctypes.c_int, [P, ctypes.c_uint64, ctypes.c_uint64, P, ctypes.c_uint64, P, P]),
+    "gevws_push_lists_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, P, P, P, ctypes.c_uint32,
+                                              P, P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P, P, P, P,
+                                              P, P]),
+    "gevws_push_plan_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64, P, P, P, P, P, P, P, P, P,
+                                             P, ctypes.c_uint32, P, P, P, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.c_uint32, P, ctypes.c_uint64, P, P]),
+    "gevws_push_check": (ctypes.c_int64, [P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "gevws_cipher_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, P, ctypes.c_uint64]),
     "gevws_synth_async": (ctypes.c_int, [P, P, P, P, ctypes.c_uint64, ctypes.c_uint64]),
     "gevws_synth_verify_async": (ctypes.c_int, [P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P,

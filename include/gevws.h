@@ -1817,6 +1817,164 @@ int gevws_fragment_offsets_async(gevws_ctx *ctx, void *stream, const uint64_t *d
 int gevws_fragment_records(const gevws_out_frame *records, uint64_t n, uint64_t max_fragment_bytes,
                            gevws_out_frame *frags, uint64_t max_frags, uint64_t *first, gevws_summary *summary);
 
+/* Server push: messages that the host originates, to every connection, to a
+ * room or to one connection (the reference's example/websocket/main.go:129-150
+ * packs "publish message" on a timer and Sends it to every session, and lines
+ * 103-115 Send from goroutines, through connection.go:122 over
+ * ws/util/util.go:10).  Additions to ABI version 3: nothing above changes.  A
+ * push pass is a chain of its own, with no decode in front:
+ *   push records + body arena -> gevws_push_lists_async -> gevws_deflate_async
+ *   (no contexts) -> gevws_encode_replies_async over the plain list and over
+ *   the deflate step's records (with gevws_fragment_async /
+ *   gevws_fragment_offsets_async around either, as in a broadcast) ->
+ *   gevws_push_plan_async -> gevws_send_gather_async with an empty wire 2.
+ * A push is framed once and compressed once, however many connections receive
+ * it; the plan names its bytes once per recipient.  The output has the shape
+ * of any other pass (d_send, d_conn_send, the gather's buffer).
+ *
+ * The record.  d_src is the body arena: device memory the caller fills, on a
+ * 16-byte boundary, with the readable slack the encoder and the deflate step
+ * ask of their payload arena.
+ *   - off / length: the body, d_src[off, off + length).  off is a multiple of
+ *     GEVWS_PAYLOAD_ALIGN.
+ *   - kind / target: GEVWS_PUSH_ALL (target 0), GEVWS_PUSH_ROOM (target = the
+ *     room, < n_rooms) or GEVWS_PUSH_CONN (target = the connection, < n_conns).
+ *   - opcode: 1 text, 2 binary, 9 ping, 10 pong.  A close frame (8) is
+ *     malformed: closing stays with the control step and the host.
+ *   - Order.  The list must not decrease in the key (kind << 32) | target.  A
+ *     recipient's pushes are then at most three contiguous slices -- the ALL
+ *     pushes, its room's, its own -- and it is sent them in list order.  The
+ *     host sorts (a stable sort keeps the order within a key); the device
+ *     checks.
+ *   - Count.  The records are the first min(d_prev->frames, max_pushes) of
+ *     d_pushes; d_prev == NULL: max_pushes.  d_prev is the summary of whatever
+ *     made the list on the device.
+ *   - Malformed, each record counted once: a kind above 2; a target out of
+ *     range, or nonzero for GEVWS_PUSH_ALL; an opcode outside {1, 2, 9, 10};
+ *     off % 16 != 0; off + length > src_bytes, or the sum overflowing; length >
+ *     2^32 - 1; a ping or pong longer than 125 bytes; a nonzero reserved byte;
+ *     a key below the previous record's.  gevws_push_check counts them on the
+ *     host by the same code (gev_amd/csrc/gevws_push.hpp).
+ *
+ * Recipients.  d_conn_live (n_conns bytes, may be NULL: every connection) says
+ * which connections of the table are sessions: n_conns is a table size, and
+ * the host clears the byte of a connection that an earlier pass shut down
+ * (GEVWS_CTL_SHUTDOWN).  An ALL push goes to every live connection, a ROOM
+ * push to the room's live members, a CONN push to its connection when it is
+ * live.  A push without recipients enters no list and no plan entry; it is not
+ * an error.  The recipient kind is the rooms' (above): a live connection takes
+ * deflate when its d_conn_ext byte has GEVWS_EXT_DEFLATE and not
+ * GEVWS_EXT_SERVER_TAKEOVER (d_conn_ext == NULL: none does), and every
+ * recipient takes a ping or a pong plain.
+ *
+ * The room tables are those of gevws_reply_rooms_async, checked on the device
+ * by the same rule before anything is indexed by them.  All three pointers may
+ * be NULL with n_rooms == n_members == 0: every connection is then
+ * GEVWS_ROOM_NONE and a ROOM push is malformed.
+ *
+ * gevws_push_lists_async
+ *   - Plain list.  Push p enters d_plain exactly when at least one of its
+ *     recipients takes it plain: a gevws_out_frame with fin 1, rsv 0, the
+ *     push's opcode, unmasked, hdr.length = payload_len = length, payload_off =
+ *     off.  It is for gevws_encode_replies_async over d_src.
+ *   - Deflate list.  Push p enters d_def_msgs exactly when its opcode is 1 or 2
+ *     and at least one recipient takes deflate: {off, length, opcode,
+ *     window_bits}.  It is for gevws_deflate_async (no contexts) over d_src.  A
+ *     push can be in both lists, in one or in neither.
+ *   - Window.  window_bits of a deflate-list entry is the smallest effective
+ *     d_conn_window_bits byte among the push's deflate-taking recipients (0, or
+ *     a NULL table, counts as 15).  The entry holds the value itself, 8..15.  A
+ *     byte outside {0, 8..15} on a live deflate-taking connection makes that
+ *     connection's record a bad table record (counted once with whatever else
+ *     is wrong with it).
+ *   - Order and indices.  Both lists keep the push order.  d_plain_of[p] /
+ *     d_def_of[p], for each of the records, = the index in that list or -1.
+ *   - Summaries.  d_plain_summary / d_def_summary: frames = the list's count,
+ *     the other fields zero.  Malformed records and bad table records add up in
+ *     `errors` of both with GEVWS_ERR_INVALID; nothing else is then written.
+ *   - Gates.  A failed d_prev or no records gives two zero summaries; nothing
+ *     else is read (no table either) or written.
+ *   - Invalid calls.  Any bit of `flags` (none is defined), max_pushes >= 2^32
+ *     or a NULL ctx is GEVWS_ERR_INVALID from the call, before any device is
+ *     touched, even with every pointer NULL.  So is a NULL summary and, with
+ *     max_pushes > 0, a NULL d_pushes or list output, or room tables that are
+ *     neither all NULL with n_rooms == n_members == 0 nor complete.
+ *
+ * gevws_push_plan_async runs behind the two encodes, or behind
+ * gevws_fragment_offsets_async where a wire was fragmented.
+ *   - Inputs.  The push list and its count as above; the list step's two
+ *     summaries and (d_plain_off, d_plain_encoded), (d_def_off, d_def_encoded)
+ *     with the meaning they have in gevws_room_plan_async: `frames` of an
+ *     encode summary is its list's count and payload_bytes its wire total.
+ *     d_plain_of / d_def_of, d_conn_ext, d_conn_live and the room tables as
+ *     above.
+ *   - Rule.  Recipient r is sent its pushes in list order.  Push p comes from
+ *     wire 1 when r takes deflate and d_def_of[p] >= 0, otherwise from wire 0.
+ *     d_send[k] = {off, len, frame = p, conn = r, wire}: off from that wire's
+ *     table at the push's list index, len to the next entry's offset or to the
+ *     wire total.
+ *   - Outputs.  d_conn_send[c] = {first, count, bytes, flags = 0} for every
+ *     connection, in connection order.  d_summary: frames = entries,
+ *     payload_bytes = the sum of len, errors = 0.  gevws_send_gather_async
+ *     runs over them unchanged.
+ *   - Capacity.  GEVWS_ERR_CAPACITY when there are more entries than
+ *     max_sends: frames and payload_bytes hold the need and nothing else is
+ *     written.
+ *   - Gates.  A failed d_prev, list summary or encode summary, no records or
+ *     n_conns == 0 give a zero summary; nothing else is read or written.
+ *   - Malformed input.  A malformed push record or a bad table record (as
+ *     above, without the window bytes), a list index outside its list's count,
+ *     an offset table that decreases at a listed push, and a push that a
+ *     recipient needs from a list it is not in (such tables cannot come from
+ *     the list step) make the call GEVWS_ERR_INVALID on the device: `errors` is
+ *     the count (a push counts once), the other fields are zero and nothing
+ *     else is written.  Every index is checked before it is used.
+ *   - Invalid calls.  Any bit of `flags`, max_pushes or max_sends >= 2^32 or a
+ *     NULL ctx is GEVWS_ERR_INVALID from the call, before any device is
+ *     touched, even with every pointer NULL.
+ *
+ * gevws_push_check: the record rule on host memory (FFI callers, the Python
+ * helper, CPU tests): the number of malformed records among records[0, n), or
+ * GEVWS_ERR_INVALID for a NULL list with n > 0 or n >= 2^32.
+ *
+ * The host's side of the order (not enforced here): a push pass's spans are
+ * written to the sockets in stream order with the passes around them, and a
+ * connection that an earlier pass shut down is marked not live before the next
+ * push. */
+#define GEVWS_PUSH_ALL 0u
+#define GEVWS_PUSH_ROOM 1u
+#define GEVWS_PUSH_CONN 2u
+typedef struct gevws_push {        /* 32 bytes */
+    uint64_t off;                  /* into d_src, a multiple of GEVWS_PAYLOAD_ALIGN */
+    uint64_t length;               /* <= 2^32 - 1; <= 125 for opcode 9 / 10 */
+    uint32_t target;               /* ALL: 0; ROOM: room < n_rooms; CONN: connection < n_conns */
+    uint8_t kind;                  /* GEVWS_PUSH_ALL / GEVWS_PUSH_ROOM / GEVWS_PUSH_CONN */
+    uint8_t opcode;                /* 1 text, 2 binary, 9 ping, 10 pong */
+    uint8_t reserved[10];          /* zero */
+} gevws_push;
+int gevws_push_lists_async(gevws_ctx *ctx, void *stream, const gevws_push *d_pushes, uint64_t max_pushes,
+                           const gevws_summary *d_prev /* may be NULL: max_pushes */, uint64_t src_bytes,
+                           const uint8_t *d_conn_ext /* may be NULL */,
+                           const uint8_t *d_conn_window_bits /* may be NULL: 15 */,
+                           const uint8_t *d_conn_live /* may be NULL: all */, uint32_t n_conns,
+                           const uint32_t *d_conn_room, const uint32_t *d_room_first,
+                           const uint32_t *d_room_members, uint32_t n_rooms, uint32_t n_members, uint32_t flags,
+                           gevws_deflate_msg *d_def_msgs, gevws_summary *d_def_summary, gevws_out_frame *d_plain,
+                           gevws_summary *d_plain_summary, int64_t *d_plain_of, int64_t *d_def_of);
+int gevws_push_plan_async(gevws_ctx *ctx, void *stream, const gevws_push *d_pushes, uint64_t max_pushes,
+                          const gevws_summary *d_prev /* may be NULL: max_pushes */, uint64_t src_bytes,
+                          const gevws_summary *d_plain_summary, const gevws_summary *d_def_summary,
+                          const int64_t *d_plain_of, const int64_t *d_def_of, const uint64_t *d_plain_off,
+                          const gevws_summary *d_plain_encoded, const uint64_t *d_def_off,
+                          const gevws_summary *d_def_encoded, const uint8_t *d_conn_ext /* may be NULL */,
+                          const uint8_t *d_conn_live /* may be NULL: all */, uint32_t n_conns,
+                          const uint32_t *d_conn_room, const uint32_t *d_room_first,
+                          const uint32_t *d_room_members, uint32_t n_rooms, uint32_t n_members, uint32_t flags,
+                          gevws_send *d_send, uint64_t max_sends, gevws_conn_send *d_conn_send,
+                          gevws_summary *d_summary);
+int64_t gevws_push_check(const gevws_push *records, uint64_t n, uint32_t n_conns, uint32_t n_rooms,
+                         uint64_t src_bytes);
+
 /* Measurement helper, not on the reference path: n bytes (n % 16 == 0, d_dst
  * 16-byte aligned, d_src any alignment) copied with the unmask kernel's
  * streaming access pattern minus the XOR and frame lookup -- the achievable
